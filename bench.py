@@ -10,9 +10,14 @@ filter range with NO data-path collective; the only collective is the end-of-run
 GPUs); the line's "scaling" and config.workload say which one ran.  `python bench.py --gpus N` starts its N ranks itself (child processes, the parent never
 touches the GPU); under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 
-The K timed steps are repeated (`repeats`) until the timed region lasts >= --min-timed-ms; `value`, `ms_per_step` and the
-roofline figures are over all `timed_steps` = K x repeats launches.  At N=1 a second leg times the same step on 1 M filters
-(state 1.17 GB, nothing cache-resident) -> roofline.frac_cache_busting.
+The timed region is exactly --steps launches (`timed_steps`), after --warmup untimed ones from the same initial state;
+`value`, `ms_per_step` and the roofline figures are over those K launches (a longer window is a larger --steps).  At N=1 a
+second leg times the same step on 1 M filters (state 1.17 GB, nothing cache-resident) -> roofline.frac_cache_busting; that leg
+repeats its 24 steps until it lasts >= --min-timed-ms.
+
+--dump-outputs DIR writes what the timed path left for its caller after the last timed step -- the head state of rank 0's
+filters as getHeadState returns it -- as DIR/<name>.npy (float64); the inputs depend on the arguments only, so two builds
+run with the same arguments can be compared output for output.
 
 Prints ONE JSON line on rank 0.
 """
@@ -239,6 +244,35 @@ def cache_busting(BatchEstimator, dev, local_rank, n, d_imu, d_lo, d_mask, vec, 
             "frac": bps * Bb / (us * 1e-6) / 1e9 / HBM_PEAK_GBPS, "value": Bb / (us * 1e-6), "nonfinite": float(s[3])}
 
 
+DUMP_BYTES = 60_000_000   # --dump-outputs budget (<= 64 MB in all, .npy headers included)
+DUMP_SEED = 20251015     # the fixed filter sample of a batch whose head state does not fit the budget
+
+
+def dump_outputs(est, summary, out_dir):
+    """The head state after the last timed step, as a caller of run_legodo receives it (get_head: vec [n,c], quat [4,c],
+    cov [n,n,c], loglik [c]), for every filter if it fits DUMP_BYTES, else for a fixed seeded sample of filters
+    (filter_index.npy says which, in increasing order); summary.npy is pb_summary over the whole batch."""
+    B, n = est.B, est.n
+    per_filter = (n + 4 + n * n + 1 + 1) * 8
+    c = min(B, DUMP_BYTES // per_filter)
+    idx = np.arange(B) if c == B else np.sort(np.random.default_rng(DUMP_SEED).choice(B, c, replace=False))
+    vec, quat, cov, ll = np.empty((n, c)), np.empty((4, c)), np.empty((n, n, c)), np.empty(c)
+    CH = 65536   # get_head in chunks: host memory stays bounded whatever the batch
+    for f0 in range(0, B, CH):
+        lo, hi = np.searchsorted(idx, [f0, min(B, f0 + CH)])
+        if lo == hi:
+            continue
+        gv, gq, gP, gll = est.get_head(f0, min(CH, B - f0))
+        sel = idx[lo:hi] - f0
+        vec[:, lo:hi], quat[:, lo:hi], cov[:, :, lo:hi], ll[lo:hi] = gv[:, sel], gq[:, sel], gP[:, :, sel], gll[sel]
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"vec": vec, "quat": quat, "cov": cov, "loglik": ll, "filter_index": idx.astype(np.float64),
+              "summary": np.asarray(summary, dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "filters": int(c), "of": int(B), "files": sorted(k + ".npy" for k in arrays)}
+
+
 def workload_name(n, Bper, total, world, scaling):
     """config.workload: BASELINE.json's own wording where the run IS one of its configs, a plain description otherwise."""
     k = lambda v: "%dk" % (v // 1024) if v % 1024 == 0 else str(v)
@@ -269,14 +303,17 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-cache-busting", action="store_true", help="skip the 1 M-filter true-HBM leg (N=1 only)")
     ap.add_argument("--min-timed-ms", type=float, default=6000.0,
-                    help="the K timed steps are repeated until the timed region is at least this long (6 s by default, for "
-                         "the 64k leg and the 1 M-filter leg alike: an external GPU-busy sampler with a 5 s period must see both)")
+                    help="the 1 M-filter legs repeat their steps until they last at least this long (6 s by default: an "
+                         "external GPU-busy sampler with a 5 s period must see them); the headline leg times exactly --steps")
     ap.add_argument("--host-streams", action="store_true",
                     help="generate the input streams with the numpy generator on the host (pronto_amd/synth.py) instead of "
                          "on the device (pronto_amd/synth_device.py: the same counter-based samples)")
     ap.add_argument("--fused", type=int, default=0, metavar="T",
                     help="also time the time-fused replay kernel (T steps per launch, state resident in registers) and "
                          "report it under its own accounting in a 'fused' object; never the headline value")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's head state (vec, quat, cov, loglik of every filter, or of a "
+                         "fixed seeded sample if that exceeds 60 MB; filter_index; the batch summary) as DIR/<name>.npy, float64")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -376,31 +413,23 @@ def main():
         elif use_dist:
             dist.barrier(device_ids=[local_rank])
 
-    # ---- warmup (untimed) ----
+    # ---- warmup (untimed): W steps and one pass over the K timed input blocks (every launch the timed region makes, at
+    # steady clocks), then a restart from x0 and the W steps again, so that the timed steps continue a plain W-step run ----
     if W:
         est.run_legodo(d_imu[:W], d_lo[:W], d_mask[:W], q4)
-    # How often the K-step block is repeated inside the timed region so that it lasts >= --min-timed-ms whatever K is
-    # (20 steps of 22 us would be a 0.4 ms measurement): one untimed calibration pass over the K steps, max over ranks.
-    reps = 1
-    if K > 0 and args.min_timed_ms > 0:
-        cal_ms = est.run_legodo(d_imu[W:], d_lo[W:], d_mask[W:], q4, timed=True)
-        r = torch.tensor([np.ceil(args.min_timed_ms / max(cal_ms, 1e-3))], dtype=torch.float64, device=cdev)
-        if use_dist:
-            dist.all_reduce(r, op=dist.ReduceOp.MAX)
-        reps = int(max(1, min(1e6, float(r[0]))))
-        # every repeat replays the same K input blocks on the state the previous one left; restart from x0 so that the
-        # timed trajectory starts where a plain K-step run would
+    if K:
+        est.run_legodo(d_imu[W:], d_lo[W:], d_mask[W:], q4)
         est.reset(vec, quat, P0)
         if W:
             est.run_legodo(d_imu[:W], d_lo[:W], d_mask[:W], q4)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
-    # ---- timed: reps x K steps = reps x K launches of the hot kernel ----
+    # ---- timed: K steps = K launches of the hot kernel ----
     ev_ms = 0.0
     t0 = time.perf_counter()
-    for _ in range(reps):
-        ev_ms += est.run_legodo(d_imu[W:], d_lo[W:], d_mask[W:], q4, timed=True)
+    if K:
+        ev_ms = est.run_legodo(d_imu[W:], d_lo[W:], d_mask[W:], q4, timed=True)
     torch.cuda.synchronize()
     barrier()
     t1 = time.perf_counter()
@@ -411,9 +440,10 @@ def main():
         dist.all_reduce(wall, op=dist.ReduceOp.MAX)
         dist.all_reduce(spread, op=dist.ReduceOp.MAX)
     wall_s, ev_s = float(wall[0]), float(wall[1])
-    KR = K * reps
 
-    summary = allreduce_summary(est.summary(), dist if use_dist else None, cdev)
+    local_summary = est.summary()
+    dumped = dump_outputs(est, local_summary, args.dump_outputs) if args.dump_outputs and rank == 0 else None
+    summary = allreduce_summary(local_summary, dist if use_dist else None, cdev)
 
     fused = None
     if args.fused > 0:  # (15 and 21 states: the cooperative replay kernel)
@@ -444,15 +474,15 @@ def main():
 
     if rank == 0:
         bps = bytes_per_step(n)
-        value = total * KR / wall_s
-        launch_s = ev_s / KR                      # HIP events on the launch stream around the launches
+        value = total * K / wall_s
+        launch_s = ev_s / K                       # HIP events on the launch stream around the launches
         achieved = bps * B / launch_s / 1e9       # algorithmic bytes of ONE launch (this rank's shard) / its duration
         state_mb = (n + 5 + n * (n + 1) // 2) * 8 * B / 1e6
         out = {
             "metric": METRIC, "value": value, "unit": "steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": wall_s / KR * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "ms_per_step": wall_s / K * 1e3, "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
-            "repeats": reps, "timed_steps": KR, "timed_region_ms": wall_s * 1e3,
+            "timed_steps": K, "timed_region_ms": wall_s * 1e3,
             "per_rank_ms": {"kernel_time_max": float(spread[0]), "kernel_time_min": -float(spread[1]),
                             "stream_generation_max": float(spread[2]) * 1e3, "stream_generation_min": -float(spread[3]) * 1e3,
                             "streams": "host numpy" if args.host_streams else "device (pronto_amd/synth_device.py)"},
@@ -489,6 +519,8 @@ def main():
                 pass
         if fused is not None:
             out["fused"] = fused
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, dt_us, args.cpu_seconds, BatchEstimator)
         print(json.dumps(out), flush=True)

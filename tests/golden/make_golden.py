@@ -169,8 +169,18 @@ def generate_notch():
     return dict(acc=acc, filtered=filt, meta=np.array([87.0, 1000.0]))
 
 
+def generate_ref_torque():
+    """The reference's TorqueAdjustment on every input of tests/test_ref_pin.py, from oracle/_ref (`make -C oracle ref` on a
+    machine with the reference tree); after leg_fk and the legodo fixtures, whose inputs it reads."""
+    import test_ref_pin
+    L = test_ref_pin.load_ref()
+    if L is None:
+        raise SystemExit("ref_torque needs oracle/_ref: make -C oracle ref")
+    return test_ref_pin.record(L)
+
+
 LEG_FIXTURES = {**{n: (lambda n=n: generate_leg(n)) for n in LEG_CASES}, "leg_fk": generate_fk, "joint_filter": generate_joint_filter,
-                "imu_notch": generate_notch}
+                "imu_notch": generate_notch, "ref_torque": generate_ref_torque}
 
 
 if __name__ == "__main__":
