@@ -435,6 +435,17 @@ int pb_state_save(pb_ctx *ctx, int slot);      /* slot <- head posterior (state,
  * A saved posterior is never modified afterwards: an update that finds the head in a slot and has no output slot of its
  * own writes back into the context's array; pb_state_restore and pb_reset always land there.  slot = -1 cancels. */
 int pb_set_output_slot(pb_ctx *ctx, int slot);
+/* The INS posterior of a fused step (EKFSmoothBackwardsPass reads it at every INS update: mav_state_est.cpp:98-189,
+ * rbis.cpp:234-266).  One-shot, like pb_set_output_slot: the NEXT pb_step_legodo / pb_step_legodo_split also writes the posterior
+ * of its process step -- what pb_predict alone would leave from the same head: bit for bit for 15 states, to rounding
+ * (1e-16 relative) for 21 -- into checkpoint `slot`, and consumes the
+ * setting whatever its outcome.  Combines with pb_set_output_slot: one call reads the head and writes two slots.  The filtered
+ * posterior is bit-identical to the same call without a predicted slot.  The 15-state two-wave step, the four-wave 21-state step and the
+ * two-wave 21-state step (PRONTO_BATCH_QUAD21=0) write both in ONE launch (k_step_quad_pred, k_step_coop_pred); k_step<15> (beyond
+ * 393 216 filters) runs the predict into the slot and the fused step as two launches.  PB_ERR_ARG: slot out of range, the pending output slot, or the slot the head lives in.
+ * pb_predict, pb_update_indexed*, pb_step_legodo_correct / _joints / _feet, pb_run_legodo and pb_replay_legodo_fused /
+ * _checkpointed with a predicted slot pending: PB_ERR_STATE (and the setting is cleared).  slot = -1 cancels. */
+int pb_set_pred_slot(pb_ctx *ctx, int slot);
 /* the checkpoint slot the head currently lives in, or -1 (the context's own array) */
 int pb_head_slot(const pb_ctx *ctx);
 int pb_state_restore(pb_ctx *ctx, int slot);   /* head posterior <- slot */
@@ -467,6 +478,16 @@ typedef void (*pb_smooth_sink)(void *user, int step, int slot);
 int pb_smooth_log_slots(int n_steps, int stride);
 int pb_smooth_log(pb_ctx *ctx, int n_steps, int stride, const double *imu_stream, const double *lo_stream, const uint8_t *mask_stream,
                   const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms);
+/* pb_smooth_log on the fused step: same arguments, slots (pb_smooth_log_slots), sink order, head afterwards and elapsed_ms.  Every
+ * step of the forward and recompute passes is ONE launch with the semantics of pb_step_legodo (two state round trips per recomputed
+ * step instead of four: in the recompute pass that launch writes the window's predicted slot, pb_set_pred_slot, and its filtered slot,
+ * pb_set_output_slot, together).  The smoothed posteriors are, bit for bit, those of the all-checkpoints pass built from
+ * pb_set_pred_slot + pb_set_output_slot + pb_step_legodo + pb_smooth_step, and agree with pb_smooth_log to rounding (the fused
+ * kernel and the two per-message kernels round differently); the head afterwards is bit-identical to n_steps pb_step_legodo calls.
+ * On an error the head is back in the context's own array (the pre-call head, or the newest posterior once the forward pass is
+ * over) and no output / predicted slot is pending. */
+int pb_smooth_log_fused(pb_ctx *ctx, int n_steps, int stride, const double *imu_stream, const double *lo_stream, const uint8_t *mask_stream,
+                        const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms);
 
 /* ---- estimator queries (mav_state_est.hpp:20-22) -------------------------------------------------------- */
 

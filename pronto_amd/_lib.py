@@ -74,6 +74,8 @@ _SIGS = {
     "pb_smooth_log_slots": (C.c_int, [C.c_int, C.c_int]),
     "pb_smooth_log": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_double, C.c_int, C.c_void_p, C.c_void_p,
                                 C.POINTER(C.c_float)]),
+    "pb_smooth_log_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_double, C.c_int, C.c_void_p,
+                                      C.c_void_p, C.POINTER(C.c_float)]),
     "pb_set_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_predict": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int]),
     "pb_update_indexed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,
@@ -122,6 +124,7 @@ _SIGS = {
     "pb_history_reserve": (C.c_int, [C.c_void_p, C.c_int]),
     "pb_state_save": (C.c_int, [C.c_void_p, C.c_int]),
     "pb_set_output_slot": (C.c_int, [C.c_void_p, C.c_int]),
+    "pb_set_pred_slot": (C.c_int, [C.c_void_p, C.c_int]),
     "pb_head_slot": (C.c_int, [C.c_void_p]),
     "pb_snapshot_from_slot": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "pb_host_alloc": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_void_p)]),

@@ -130,6 +130,11 @@ class BatchEstimator:
         per update without a copy.  -1 cancels."""
         self._chk(self._L.pb_set_output_slot(self._h, int(slot)))
 
+    def set_pred_slot(self, slot):
+        """The next step_legodo / step_legodo_split also writes its INS posterior (the prediction, before the leg-odometry update)
+        into checkpoint `slot`.  One-shot: that call consumes it whatever its outcome.  -1 cancels."""
+        self._chk(self._L.pb_set_pred_slot(self._h, int(slot)))
+
     def state_save(self, slot):
         self._chk(self._L.pb_state_save(self._h, slot))
 
@@ -142,9 +147,10 @@ class BatchEstimator:
     def smooth_log_slots(self, n_steps, stride):
         return self._L.pb_smooth_log_slots(n_steps, stride)
 
-    def smooth_log(self, imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot=0, sink=None, timed=False):
+    def smooth_log(self, imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot=0, sink=None, timed=False, fused=False):
         """Whole-log RTS smoothing with bounded memory (checkpoint and recompute): sink(step, slot) is called newest step first; read the
-        slot with get_slot before returning from the sink.  Returns device ms if timed."""
+        slot with get_slot before returning from the sink.  Returns device ms if timed.  fused: pb_smooth_log_fused (one fused launch
+        per step, as step_legodo) instead of pb_smooth_log (the process step and the update as two launches)."""
         T = imu_stream.shape[0]
         pi, m1 = _ptr(imu_stream, shape=(T, 7, self.B))
         pl, m2 = _ptr(lo_stream, shape=(T, 6, self.B))
@@ -155,9 +161,14 @@ class BatchEstimator:
         ms = C.c_float(0)
         SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)
         cb = SINK((lambda user, step, slot: sink(step, slot))) if sink is not None else None
-        self._chk(self._L.pb_smooth_log(self._h, T, stride, pi, pl, pm, q, dt, first_slot, C.cast(cb, C.c_void_p) if cb else None, None,
-                                        C.byref(ms) if timed else None))
+        fn = self._L.pb_smooth_log_fused if fused else self._L.pb_smooth_log
+        self._chk(fn(self._h, T, stride, pi, pl, pm, q, dt, first_slot, C.cast(cb, C.c_void_p) if cb else None, None,
+                     C.byref(ms) if timed else None))
         return ms.value if timed else None
+
+    def smooth_log_fused(self, imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot=0, sink=None, timed=False):
+        """smooth_log on pb_smooth_log_fused: every forward and recompute step is ONE fused launch (step_legodo's semantics)."""
+        return self.smooth_log(imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot, sink, timed, fused=True)
 
     def get_slot(self, slot, first=0, count=None, want_cov=True):
         """get_head for a posterior that lives in a checkpoint slot."""

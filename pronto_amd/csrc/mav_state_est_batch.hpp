@@ -284,6 +284,9 @@ public:
   void announce(pb_ctx *ctx) const { if (valid_dev) pb_set_imu_valid(ctx, valid_dev); }
   BatchArray imu_block;
   double q_gyro, q_accel, q_gyro_bias, q_accel_bias;
+  // set by MavStateEstimator when this step last ran fused with the update behind it (fuse_ins_legodo): its own posterior then has no
+  // checkpoint, and EKFSmoothBackwardsPass re-derives it by re-applying the pair with a predicted slot (pb_set_pred_slot)
+  bool ran_fused = false;
   RBISIMUProcessStep(BatchArray imu_block_, double q_gyro_, double q_accel_, double q_gyro_bias_, double q_accel_bias_,
                      int64_t utime)
       : RBISUpdateInterface(ins, utime), imu_block(imu_block_), q_gyro(q_gyro_), q_accel(q_accel_),
@@ -672,6 +675,7 @@ public:
                   last_status = rc;
                   fprintf(stderr, "MavStateEstimator::addUpdate: fused ins+legodo+correction step failed: %s\n", pb_last_error(ctx));
                 }
+                imu->ran_fused = false;   // (triples: no checkpoints, no smoother pass)
                 fused_triples++;
                 device_head = third->second;
                 head_utime = third->second->utime;
@@ -690,6 +694,7 @@ public:
                 last_status = rc;
                 fprintf(stderr, "MavStateEstimator::addUpdate: fused ins+legodo step failed: %s\n", pb_last_error(ctx));
               }
+              imu->ran_fused = true;
               fused_pairs++;
               device_head = nxt->second;
               head_utime = nxt->second->utime;
@@ -710,6 +715,7 @@ public:
       int slot = -1;
       if (history_slots > 0 && ++since_checkpoint >= checkpoint_every && (slot = reserve_slot(u)) >= 0)
         pb_set_output_slot(ctx, slot);
+      if (auto *imu = dynamic_cast<RBISIMUProcessStep *>(u)) imu->ran_fused = false;
       int rc = u->updateFilter(ctx);
       if (rc != PB_OK) {
         last_status = rc;
@@ -853,14 +859,15 @@ public:
   // The reference overwrites the updates' posteriors with the smoothed ones for later republishing; here
   // on_smoothed(utime of INS_k, slot) is called newest-first with a slot that holds the smoothed posterior until the next call
   // (pb_get_slot reads it; pb_state_restore(slot) + getHeadState too).  Returns the number of steps, -1 on an error.
+  // With fuse_ins_legodo an INS update that ran fused with the update behind it has no posterior of its own (the pair kernel keeps the
+  // prediction in registers): the pass treats it as missing and re-applies the PAIR in one fused launch that writes the prediction
+  // into the INS update's window slot (pb_set_pred_slot) and the pair's posterior into the partner's (pb_set_output_slot) -- never
+  // into an existing checkpoint: when the partner has one, into one more window slot.
   int64_t smoother_reapplied_updates = 0;   // statistics: updates re-applied to re-derive posteriors that had no checkpoint
+  int64_t smoother_reapplied_pairs = 0;     // ... of which fused INS + leg-odometry pairs, re-applied as one launch (each counts once)
   int EKFSmoothBackwardsPass(double dt, const std::function<void(int64_t, int)> &on_smoothed)
   {
     auto &map = history.updateMap;
-    if (fuse_ins_legodo) {
-      fprintf(stderr, "EKFSmoothBackwardsPass: needs the posterior of every INS update; run with state_estimator.fuse_ins_legodo = false\n");
-      return -1;
-    }
     flushPending();
     // time-ordered list of (update, slot or -1)
     std::vector<std::pair<RBISUpdateInterface *, int>> seq;
@@ -883,11 +890,13 @@ public:
     int maxgap = N - 1 - cks.back();
     for (size_t m = 0; m + 1 < cks.size(); m++) maxgap = std::max(maxgap, cks[m + 1] - cks[m] - 1);
     const bool head_loose = seq.back().second < 0;   // the newest posterior exists only as the device head
-    const int need = maxgap + 2 + ((maxgap > 0 || head_loose) ? 1 : 0);
+    const bool pair_out = fuse_ins_legodo && maxgap > 0;   // a re-applied pair whose partner has a checkpoint writes one slot further
+    const int need = maxgap + 2 + ((maxgap > 0 || head_loose) ? 1 : 0) + (pair_out ? 1 : 0);
     if ((int) free_slots.size() < need) {
-      fprintf(stderr, "EKFSmoothBackwardsPass: needs %d free checkpoint slots (two for the smoothed posteriors%s), %zu are free: raise "
+      fprintf(stderr, "EKFSmoothBackwardsPass: needs %d free checkpoint slots (two for the smoothed posteriors%s%s), %zu are free: raise "
                       "state_estimator.history_slots or lower history_checkpoint_every\n",
-              need, maxgap > 0 ? ", the longest run of updates without a checkpoint and one for the head" : "", free_slots.size());
+              need, maxgap > 0 ? ", the longest run of updates without a checkpoint and one for the head" : (head_loose ? ", one for the head" : ""),
+              pair_out ? ", one for the posterior of a re-applied fused pair" : "", free_slots.size());
       return -1;
     }
     const size_t nf = free_slots.size();
@@ -917,6 +926,22 @@ public:
       if (last_missing > a) {                          // re-derive the posteriors of a+1 .. last_missing into the window
         if ((rc = pb_state_restore(ctx, seq[(size_t) a].second)) != PB_OK) return bail("restoring a checkpoint");
         for (int i = a + 1; i <= last_missing; i++) {
+          auto *imu = dynamic_cast<RBISIMUProcessStep *>(seq[(size_t) i].first);
+          if (imu != nullptr && imu->ran_fused && i + 1 <= e) {   // the pair: prediction -> W(i - a - 1), posterior -> W(i - a)
+            pb_set_output_slot(ctx, W(i - a));
+            if ((rc = pb_set_pred_slot(ctx, W(i - a - 1))) != PB_OK) return bail("setting the predicted slot");
+            if (run_fused(imu, seq[(size_t) i + 1].first, rc)) {
+              if (rc != PB_OK) return bail("re-applying a fused pair");
+              smoother_reapplied_updates += 2;
+              smoother_reapplied_pairs++;
+              i++;
+              continue;
+            }
+            // no fused re-application of this partner (a six-row leg-odometry measurement whose pair kernel has run): the two
+            // halves one after the other -- the prediction exactly, the partner's posterior to rounding of the pair kernel's
+            pb_set_pred_slot(ctx, -1);
+            pb_set_output_slot(ctx, -1);
+          }
           pb_set_output_slot(ctx, W(i - a - 1));
           if ((rc = seq[(size_t) i].first->updateFilter(ctx)) != PB_OK) return bail("re-applying an update");
           smoother_reapplied_updates++;

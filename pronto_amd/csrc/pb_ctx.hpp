@@ -28,6 +28,7 @@ struct pb_ctx {
   double *st = nullptr;       // the HEAD posterior: st_base, or a checkpoint slot an update wrote its posterior into
   double *st_base = nullptr;  // the context's own state array
   int out_slot = -1;          // pb_set_output_slot: where the next update writes (then that slot is the head)
+  int pred_slot = -1;         // pb_set_pred_slot: where the next fused step also writes its predicted posterior (one-shot)
   double *snaps = nullptr, *d_small = nullptr;
   double *hist = nullptr;  // posterior checkpoint slots (pb_history_reserve)
   int nhist = 0;
@@ -159,6 +160,10 @@ int pbk_step_leg15(pb_ctx *c, double *out, const double *imu, const double q[4],
 int pbk_step_leg21(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin, const LegStepArgs &la);
 // slot0 >= 0: write-through -- the posterior of step t also goes to checkpoint slot slot0 + t (pb_replay_legodo_checkpointed)
 int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, const uint8_t *mask, const double q[4], int slot0 = -1);
+// pb_step_pred.hip: the fused step that also writes its predicted posterior into `pred` (k_step_coop_pred); -1 = this context has no
+// such kernel (pbk_step then runs the predict into `pred` and the fused step as two launches)
+int pbk_step_pred_kernel(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
+                         const StepBcast &bc);
 // predict + leg-odometry update + a second (orientation) update in one state round trip; corr_kind = enum pb_corr
 int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                      const double *z2, const double *r2, const double *rb2, const double *qm2, const uint8_t *mask2,

@@ -70,10 +70,38 @@ int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t
   return PB_OK;
 }
 
+// The fused step with a predicted slot pending (pb_set_pred_slot, consumed here): one launch that writes both posteriors where a kernel
+// for it exists (k_step_coop_pred), otherwise the predict alone into the slot -- the head stays where it is -- and the fused step
+// behind it.  Either way the filtered posterior is the fused step's, bit for bit, and the slot holds what pb_predict would leave.
+static int step_pred(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bc)
+{
+  double *pred = c->hist + (size_t) c->pred_slot * c->state_doubles;
+  const int ps = c->pred_slot;
+  c->pred_slot = -1;
+  int rc = PB_OK;
+  imu = pbk_idle_prepare(c, imu, &rc);   // (once: both launches of the fall-back read the same prepared block)
+  if (rc) return rc;
+  double *out = update_target(c);
+  if (pbk_step_pred_kernel(c, out, pred, imu, lo, mask, q, bc) == PB_OK) {
+    LAUNCHCHK(c);
+    update_done(c, out);
+    return PB_OK;
+  }
+  double *head = c->st;
+  const int os = c->out_slot;
+  c->out_slot = ps;
+  rc = launch_step<false>(c, imu, nullptr, nullptr, q, bc);
+  c->st = head;
+  c->out_slot = os;
+  if (rc) return rc;
+  return launch_step<true>(c, imu, lo, mask, q, bc);
+}
+
 int pbk_step(pb_ctx *c, bool update, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
              const StepBcast *bcast)
 {
   const StepBcast bc = bcast ? *bcast : StepBcast();
+  if (update && c->pred_slot >= 0) return step_pred(c, imu, lo, mask, q, bc);
   return update ? launch_step<true>(c, imu, lo, mask, q, bc) : launch_step<false>(c, imu, nullptr, nullptr, q, bc);
 }
 

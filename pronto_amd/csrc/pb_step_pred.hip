@@ -1,0 +1,35 @@
+// pb_step_pred.hip -- the fused step that also keeps its prediction (pb_set_pred_slot): k_step_coop_pred / k_step_quad_pred, one object of its own so
+// that the step kernels' object (pb_step.hip) stays what it was.
+#include "pb_ctx.hpp"
+
+template <int MH>
+static int launch_pred_mh(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
+                          const StepBcast &bc)
+{
+  const int B = c->B;
+  if (c->ns == 15 && c->coop15) {
+    Consts kk = c->k;
+    kk.half_tiles = c->half15 ? 1 : 0;   // (as launch_step_mh: this launch only)
+    k_step_coop_pred<15, MH><<<nblk(B) * (c->half15 ? 2 : 1), 128, 0, c->stream>>>(c->st, out, pred, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, bc);
+    return PB_OK;
+  }
+  if (c->ns == 21 && c->quad21) {
+    k_step_quad_pred<MH><<<nblk(B), 256, 0, c->stream>>>(c->st, out, pred, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    return PB_OK;
+  }
+  if (c->ns == 21) {
+    k_step_coop_pred<21, MH><<<nblk(B), 128, 0, c->stream>>>(c->st, out, pred, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    return PB_OK;
+  }
+  return -1;
+}
+
+int pbk_step_pred_kernel(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
+                         const StepBcast &bc)
+{
+  switch (c->mem_hint) {
+  case MH_STORE_SC1: return launch_pred_mh<MH_STORE_SC1>(c, out, pred, imu, lo, mask, q, bc);
+  case MH_STREAM_NT: return launch_pred_mh<MH_STREAM_NT>(c, out, pred, imu, lo, mask, q, bc);
+  default: return launch_pred_mh<MH_DEFAULT>(c, out, pred, imu, lo, mask, q, bc);
+  }
+}

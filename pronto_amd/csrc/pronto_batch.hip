@@ -520,10 +520,37 @@ const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out)
   return c->imu_keep;
 }
 
+// pb_set_pred_slot belongs to the next pb_step_legodo / pb_step_legodo_split, and that call consumes it whatever becomes of it
+// (PredTake).  The other entry points that take an IMU step or an update do not write a predicted posterior: with one pending
+// they refuse and forget it (refuse_pred).
+struct PredTake {
+  pb_ctx *c;
+  explicit PredTake(pb_ctx *ctx) : c(ctx) {}
+  ~PredTake()
+  {
+    if (c) c->pred_slot = -1;
+  }
+};
+static int refuse_pred(pb_ctx *c, const char *fn)
+{
+  if (!c || c->pred_slot < 0) return PB_OK;
+  c->pred_slot = -1;
+  return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / pb_step_legodo_split)", fn);
+}
+// the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
+static int check_pred(pb_ctx *c)
+{
+  if (c->pred_slot < 0) return PB_OK;
+  if (c->pred_slot >= c->nhist || c->pred_slot == c->out_slot || c->pred_slot == pb_head_slot(c))
+    return fail(c, PB_ERR_ARG, "predicted slot %d: out of range, the output slot or the head's slot", c->pred_slot);
+  return PB_OK;
+}
+
 extern "C" int pb_predict(pb_ctx *c, const double *imu_block, const double q[4], int mem)
 {
   ImuIdleTake idle(c);
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_predict")) return rc;
   NEED_STATE(c);
   if (!imu_block || !q) return fail(c, PB_ERR_ARG, "pb_predict: NULL input");
   if (mem == PB_HOST_BROADCAST) {  // one message for every filter: the 7 values are kernel arguments
@@ -542,8 +569,10 @@ extern "C" int pb_step_legodo(pb_ctx *c, const double *imu_block, const double *
                               const double q[4], int mem)
 {
   ImuIdleTake idle(c);
+  PredTake pred(c);
   ENTER(c);
   NEED_STATE(c);
+  if (int rc = check_pred(c)) return rc;
   if (!imu_block || !lo_block || !q) return fail(c, PB_ERR_ARG, "pb_step_legodo: NULL input");
   if (mem == PB_HOST_BROADCAST) {
     // one message for every filter (a parameter sweep replaying one robot's log): the 13 values are kernel arguments --
@@ -566,9 +595,11 @@ extern "C" int pb_step_legodo_split(pb_ctx *c, const double *imu_block, int imu_
                                     const uint8_t *mask, int lo_mem, const double q[4])
 {
   ImuIdleTake idle(c);
-  if (imu_mem == lo_mem) return pb_step_legodo(c, imu_block, lo_block, mask, q, imu_mem);
+  if (imu_mem == lo_mem) return pb_step_legodo(c, imu_block, lo_block, mask, q, imu_mem);   // (which consumes a predicted slot)
+  PredTake pred(c);
   ENTER(c);
   NEED_STATE(c);
+  if (int rc = check_pred(c)) return rc;
   if (!imu_block || !lo_block || !q) return fail(c, PB_ERR_ARG, "pb_step_legodo_split: NULL input");
   if (imu_mem == PB_HOST && lo_mem == PB_HOST) return fail(c, PB_ERR_ARG, "pb_step_legodo_split: unreachable");
   StepBcast bc;
@@ -605,6 +636,7 @@ extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const 
 {
   ImuIdleTake idle(c);
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_step_legodo_correct")) return rc;
   NEED_STATE(c);
   if (!imu_block || !lo_block || !q || !z2 || !R2 || !quat_meas2) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: NULL input");
   if (corr_kind != PB_CORR_POS_ORIENT && corr_kind != PB_CORR_POS_YAW) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: bad corr_kind %d", corr_kind);
@@ -645,6 +677,7 @@ extern "C" int pb_run_legodo(pb_ctx *c, int n_steps, const double *imu_stream, c
                              const uint8_t *mask_stream, const double q[4], float *elapsed_ms)
 {
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_run_legodo")) return rc;
   NEED_STATE(c);
   if (n_steps < 0 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_run_legodo: bad argument");
   const size_t B = (size_t) c->B;
@@ -702,6 +735,7 @@ extern "C" int pb_replay_legodo_fused(pb_ctx *c, int n_steps, int steps_per_laun
                                       float *elapsed_ms)
 {
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_replay_legodo_fused")) return rc;
   NEED_STATE(c);
   if (n_steps < 0 || steps_per_launch < 1 || !imu_stream || !lo_stream || !q)
     return fail(c, PB_ERR_ARG, "pb_replay_legodo_fused: bad argument");
@@ -730,6 +764,7 @@ extern "C" int pb_replay_legodo_checkpointed(pb_ctx *c, int n_steps, int steps_p
                                              float *elapsed_ms)
 {
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_replay_legodo_checkpointed")) return rc;
   NEED_STATE(c);
   if (n_steps < 0 || steps_per_launch < 1 || !imu_stream || !lo_stream || !q)
     return fail(c, PB_ERR_ARG, "pb_replay_legodo_checkpointed: bad argument");
@@ -808,12 +843,14 @@ static int update_common(pb_ctx *c, int m, const int *idx, const double *z, cons
 extern "C" int pb_update_indexed(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int r_kind,
                                  const uint8_t *mask, int mem)
 {
+  if (int rc = refuse_pred(c, "pb_update_indexed")) return rc;
   return update_common(c, m, idx, z, R, r_kind, nullptr, false, mask, mem);
 }
 
 extern "C" int pb_update_indexed_orient(pb_ctx *c, int m, const int *idx, const double *z, const double *R,
                                         int r_kind, const double *quat_meas, const uint8_t *mask, int mem)
 {
+  if (int rc = refuse_pred(c, "pb_update_indexed_orient")) return rc;
   return update_common(c, m, idx, z, R, r_kind, quat_meas, true, mask, mem);
 }
 
@@ -1577,6 +1614,7 @@ extern "C" int pb_step_legodo_joints(pb_ctx *c, const double *imu_block, int imu
   ImuIdleTake idle(c);
   const LegMsgTimes mt = leg_take_message_times(c);
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_step_legodo_joints")) return rc;
   NEED_STATE(c);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_step_legodo_joints before pb_legodo_init");
   if (!imu_block || !q || !forces || (lo_block_out && !mask_out)) return fail(c, PB_ERR_ARG, "pb_step_legodo_joints: NULL input");
@@ -1595,6 +1633,7 @@ extern "C" int pb_step_legodo_feet(pb_ctx *c, const double *imu_block, int imu_m
   ImuIdleTake idle(c);
   const LegMsgTimes mt = leg_take_message_times(c);
   ENTER(c);
+  if (int rc = refuse_pred(c, "pb_step_legodo_feet")) return rc;
   NEED_STATE(c);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_step_legodo_feet before pb_legodo_init");
   if (!imu_block || !q || !feet || !forces || (lo_block_out && !mask_out)) return fail(c, PB_ERR_ARG, "pb_step_legodo_feet: NULL input");
@@ -1782,6 +1821,7 @@ extern "C" int pb_history_reserve(pb_ctx *c, int n_slots)
   if (c->hist) HIPCHK(c, hipFree(c->hist));
   c->hist = nullptr;
   c->nhist = 0;
+  c->pred_slot = -1;
   if (n_slots == 0) return PB_OK;
   const size_t bytes = sizeof(double) * c->state_doubles;
   hipError_t e = hipMalloc((void **) &c->hist, bytes * n_slots);
@@ -1798,6 +1838,20 @@ extern "C" int pb_set_output_slot(pb_ctx *c, int slot)
   ENTER(c);
   if (slot < -1 || slot >= c->nhist) return fail(c, PB_ERR_STATE, "pb_set_output_slot: checkpoint slot %d of %d", slot, c->nhist);
   c->out_slot = slot;
+  return PB_OK;
+}
+
+extern "C" int pb_set_pred_slot(pb_ctx *c, int slot)
+{
+  ENTER(c);
+  if (slot == -1) {
+    c->pred_slot = -1;
+    return PB_OK;
+  }
+  if (slot < 0 || slot >= c->nhist) return fail(c, PB_ERR_ARG, "pb_set_pred_slot: checkpoint slot %d of %d", slot, c->nhist);
+  if (slot == c->out_slot) return fail(c, PB_ERR_ARG, "pb_set_pred_slot: slot %d is the pending output slot", slot);
+  if (slot == pb_head_slot(c)) return fail(c, PB_ERR_ARG, "pb_set_pred_slot: slot %d holds the head", slot);
+  c->pred_slot = slot;
   return PB_OK;
 }
 
@@ -1922,6 +1976,82 @@ extern "C" int pb_smooth_log(pb_ctx *c, int n_steps, int stride, const double *i
   }
   rc = pb_state_restore(c, FIN);
   if (rc) return rc;
+  if (elapsed_ms) {
+    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+    HIPCHK(c, hipEventSynchronize(c->ev1));
+    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
+  }
+  return PB_OK;
+}
+
+// pb_smooth_log with the fused step: every step of the forward pass and of the recompute pass is ONE launch with the semantics of
+// pb_step_legodo; in the recompute pass that launch writes the window's predicted slot (pb_set_pred_slot) and its filtered slot
+// together.  Same slots, sink order and head afterwards as pb_smooth_log.  On an error the head goes back to the context's own
+// array (the pre-call head, or the newest posterior once the forward pass is over) and no output / predicted slot is left pending.
+extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
+                                   const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink,
+                                   void *user, float *elapsed_ms)
+{
+  ENTER(c);
+  c->pred_slot = -1;
+  NEED_STATE(c);
+  int rc = detach_head(c, true);
+  if (rc) return rc;
+  if (n_steps < 1 || stride < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_smooth_log_fused: bad argument");
+  const int K = stride, T = n_steps, M = (T + K - 1) / K, need = pb_smooth_log_slots(T, K);
+  if (first_slot < 0 || first_slot + need > c->nhist)
+    return fail(c, PB_ERR_STATE, "pb_smooth_log_fused: needs checkpoint slots [%d, %d), %d are reserved (pb_history_reserve)", first_slot,
+                first_slot + need, c->nhist);
+  const size_t B = (size_t) c->B, n = c->state_doubles;
+  const int CK = first_slot, WP = CK + M, WF = WP + K, PC = WF + K, FIN = PC + 1, SP = FIN + 1;   // (as pb_smooth_log)
+  auto slot_ptr = [&](int sl) { return c->hist + (size_t) sl * n; };
+  bool have_fin = false;
+  auto bail = [&](int code) -> int {
+    c->out_slot = -1;
+    c->pred_slot = -1;
+    if (c->st != c->st_base) {   // (backward pass: the head lives in a checkpoint or window slot)
+      if (have_fin) (void) hipMemcpyAsync(c->st_base, slot_ptr(FIN), sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream);
+      c->st = c->st_base;
+    }
+    return code;
+  };
+  // one step of the log as pb_step_legodo applies it (pred_slot / filt_slot < 0: in place)
+  auto step = [&](int j, int pred_slot, int filt_slot) -> int {
+    c->pred_slot = pred_slot;
+    c->out_slot = filt_slot;
+    const int r = pbk_step(c, true, imu_stream + (size_t) j * 7 * B, lo_stream + (size_t) j * 6 * B, mask_stream ? mask_stream + (size_t) j * B : nullptr, q);
+    c->pred_slot = -1;
+    return r;
+  };
+  if (elapsed_ms && hipEventRecord(c->ev0, c->stream) != hipSuccess) return bail(fail(c, PB_ERR_HIP, "pb_smooth_log_fused: hipEventRecord"));
+  // ---- forward: the filter, a checkpoint in front of every stretch ----
+  for (int j = 0; j < T; j++) {
+    if (j % K == 0 && (rc = pb_state_save(c, CK + j / K))) return bail(rc);
+    if ((rc = step(j, -1, -1))) return bail(rc);
+  }
+  if ((rc = pb_state_save(c, FIN))) return bail(rc);
+  have_fin = true;
+  // ---- backward: stretch by stretch ----
+  int next_sm = FIN, toggle = 0;
+  for (int m = M - 1; m >= 0; m--) {
+    const int s0 = m * K, s1 = std::min(T, s0 + K) - 1;
+    c->st = slot_ptr(CK + m);
+    c->out_slot = -1;
+    for (int j = s0; j <= s1; j++)
+      if ((rc = step(j, WP + (j - s0), WF + (j - s0)))) return bail(rc);
+    for (int j = s1; j >= s0; j--) {
+      if (j == T - 1) continue;
+      const int np = (j == s1) ? PC : WP + (j + 1 - s0);
+      const int out = SP + toggle;
+      if ((rc = pbk_smooth_step(c, slot_ptr(np), slot_ptr(next_sm), slot_ptr(WF + (j - s0)), slot_ptr(out), dt))) return bail(rc);
+      if (sink) sink(user, j, out);
+      next_sm = out;
+      toggle ^= 1;
+    }
+    if (hipMemcpyAsync(slot_ptr(PC), slot_ptr(WP), sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+      return bail(fail(c, PB_ERR_HIP, "pb_smooth_log_fused: carry copy"));
+  }
+  if ((rc = pb_state_restore(c, FIN))) return bail(rc);
   if (elapsed_ms) {
     HIPCHK(c, hipEventRecord(c->ev1, c->stream));
     HIPCHK(c, hipEventSynchronize(c->ev1));

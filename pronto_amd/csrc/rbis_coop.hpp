@@ -165,6 +165,12 @@ __device__ __forceinline__ void pb_pin(double &v) { asm volatile("" : "+v"(v)); 
 #else
 inline void pb_pin(double &) {}
 #endif
+// SP: where a role stores its rows of the PREDICTED posterior (k_step_coop_pred: a checkpoint slot, through a second TileIO).  The
+// default stores nothing and compiles to nothing: every other kernel is the code it was.
+struct NoPredStore {
+  static constexpr bool on = false;
+  PB_HD void operator()(int, double) const {}
+};
 struct SixIn {
   double z[3] = { 0.0, 0.0, 0.0 }, r = 1.0;
   bool on = false;
@@ -185,10 +191,12 @@ struct SixIn {
 //      downdates its sub-matrix with them and runs the velocity block on the result: no extra barrier.
 //   2  pos_and_lin_rate: the velocity block, then CORR = CorrPos on its posterior with the correction summed (the CORR stage
 //      otherwise is a second, separate update: two addState calls, like the reference's two updateFilter calls).
-template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, bool LEG = false, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC>
+template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, bool LEG = false, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC,
+          class SP = NoPredStore>
 PB_HD void coop_role_core(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k,
-                          const CorrInputs &cin_ = CorrInputs())
+                          const CorrInputs &cin_ = CorrInputs(), SP sp = SP())
 {
+  static_assert(!SP::on || (PREDICT && UPDATE && CORR::M == 0 && !LEG && SIX == 0), "the predicted rows: the plain fused step only");
   static_assert(!LEG || (UPDATE && PREDICT), "the odometry wave feeds a predict + update step");
   static_assert(SIX == 0 || (UPDATE && PREDICT), "the six-row leg-odometry modes ride on a predict + velocity update");
   static_assert(SIX != 2 || (CORR::M == 3 && !CORR::ORIENT), "SIX == 2: the second block is a 3-row vector block of role C's states");
@@ -276,6 +284,19 @@ PB_HD void coop_role_core(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInput
   // ---- state propagate (rbis.cpp:37-75); omega/accel entries are role P's to store ----
   ins_update_state<NS>(x, q, in.gyro, in.accel, in.dt, k);
   }  // PREDICT
+  if constexpr (SP::on) {
+    // the predicted posterior, exactly what the predict-only flavour stores below: this role's sub-matrix, state, quaternion and
+    // (unchanged) log-likelihood -- stored now, while the update is still to come (it overwrites these very registers)
+#pragma unroll
+    for (int i = 0; i < NSC; i++)
+#pragma unroll
+      for (int j = 0; j <= i; j++) sp(L::OFF_P + pk(C::fullc(i), C::fullc(j)), Pc[pk(i, j)]);
+#pragma unroll
+    for (int i = 0; i < NSC; i++) sp(L::OFF_VEC + C::fullc(i), x[C::fullc(i)]);
+#pragma unroll
+    for (int i = 0; i < 4; i++) sp(L::OFF_QUAT + i, q[i]);
+    if constexpr (!C::LL_IN_P) sp(L::OFF_LL, ll);
+  }
 
   double dfull[NS];   // the velocity block's correction (SIX == 2: applied together with the second block's)
 #pragma unroll
@@ -517,10 +538,12 @@ PB_HD void coop_role_core(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInput
 // role P: passive panels P_cp, P_bp, P_pp and the omega / accel entries of x.   XR(slot) reads the hand-off.
 // ------------------------------------------------------------------------------------------------------------
 // SIX == 1: this role applies the angular-velocity block of lin_rot_rate (see coop_role_core) -- XW publishes its factors.
-template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC>
+template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC,
+          class SP = NoPredStore>
 PB_HD void coop_role_passive_x(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k,
-                               const CorrInputs &cin = CorrInputs(), const SixIn &six = SixIn())
+                               const CorrInputs &cin = CorrInputs(), const SixIn &six = SixIn(), SP sp = SP())
 {
+  static_assert(!SP::on || (PREDICT && UPDATE && CORR::M == 0 && SIX == 0), "the predicted rows: the plain fused step only");
   static_assert(SIX != 1 || (UPDATE && PREDICT && CORR::M == 0), "SIX == 1 rides on a predict + velocity update");
   using L = Lay<NS>;
   using C = Coop<NS>;
@@ -600,6 +623,23 @@ PB_HD void coop_role_passive_x(LD ld, ST st, XW xw, XR xr, SYNC sync, const Step
     xp[3 + i] = in.accel[i] - (C::HB ? x[18 + i] : 0.0);
   }
   }  // PREDICT
+  if constexpr (SP::on) {  // the predicted panels, P_pp, omega / accel entries (and log-likelihood): see coop_role_core
+#pragma unroll
+    for (int J = 0; J < 2; J++)
+#pragma unroll
+      for (int sb = 0; sb < NSB; sb++)
+#pragma unroll
+        for (int r = 0; r < 3; r++)
+#pragma unroll
+          for (int c = 0; c < 3; c++) sp(L::OFF_P + pk(C::fullc(3 * sb + r), C::fullp(3 * J + c)), X[sb][J][3 * r + c]);
+#pragma unroll
+    for (int i = 0; i < 6; i++)
+#pragma unroll
+      for (int j = 0; j <= i; j++) sp(L::OFF_P + pk(C::fullp(i), C::fullp(j)), Ppp[pk(i, j)]);
+    if constexpr (C::LL_IN_P) sp(L::OFF_LL, ll);
+#pragma unroll
+    for (int i = 0; i < 6; i++) sp(L::OFF_VEC + C::fullp(i), xp[i]);
+  }
 
   if constexpr (SIX == 1) {
     // ---- the angular-velocity block: S = (q_gyro + r) I, W = P'[:, omega], no factorisation ----
@@ -789,11 +829,11 @@ PB_HD void coop_role_passive_x(LD ld, ST st, XW xw, XR xr, SYNC sync, const Step
 #pragma unroll
   for (int i = 0; i < 6; i++) st(L::OFF_VEC + C::fullp(i), xp[i]);
 }
-template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, class LD, class ST, class XR, class SYNC>
+template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, class LD, class ST, class XR, class SYNC, class SP = NoPredStore>
 PB_HD void coop_role_passive(LD ld, ST st, XR xr, SYNC sync, const StepInputs &in, const Consts &k,
-                             const CorrInputs &cin = CorrInputs())
+                             const CorrInputs &cin = CorrInputs(), SP sp = SP())
 {
-  coop_role_passive_x<NS, UPDATE, CORR, PREDICT, 0>(ld, st, [](int, double) {}, xr, sync, in, k, cin);
+  coop_role_passive_x<NS, UPDATE, CORR, PREDICT, 0>(ld, st, [](int, double) {}, xr, sync, in, k, cin, SixIn(), sp);
 }
 
 }  // namespace pb

@@ -703,6 +703,74 @@ __global__ __launch_bounds__(128, 1) void k_step_coop(const double *st, double *
   }
 }
 
+// A role's rows of the predicted posterior into a second tile (k_step_coop_pred, k_step_quad_pred): the role bodies' SP functor.
+template <class IO>
+struct PredStore {
+  static constexpr bool on = true;
+  IO *io;
+  __device__ __forceinline__ void operator()(int comp, double v) const { io->st(comp, v); }
+};
+
+// k_step_coop<NS, true> (plain fused step) that also writes the PREDICTED posterior -- the INS update's, before the leg-odometry
+// update behind it: what k_step_coop<NS, false> alone leaves -- into `pred`, a checkpoint slot of the same tiled layout
+// (pb_set_pred_slot).  Each role stores its own rows of it the moment its predict is final (SP, rbis_coop.hpp) and goes on with the
+// update; the filtered posterior is the same arithmetic, bit for bit.  A kernel of its own rather than a flag of k_step_coop, so
+// that every launch without a predicted slot runs the code object it ran before; same inputs, same input order.
+template <int NS, int MH = MH_DEFAULT>
+__global__ __launch_bounds__(128, 1) void k_step_coop_pred(const double *st, double *sto, double *pred, int B,
+                                                           const double *__restrict__ imu, const double *__restrict__ lo,
+                                                           const uint8_t *__restrict__ mask, double qg, double qa,
+                                                           double qbg, double qba, Consts k, StepBcast bc)
+{
+  __shared__ double xch[CoopX<NS, NoCorr>::NXCH][64];
+  const int role = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+  const unsigned wgi = xcd_workgroup(k);   // (half tiles: as k_step_coop)
+  const unsigned tile = k.half_tiles ? (wgi >> 1) : wgi;
+  const unsigned lane = k.half_tiles ? ((threadIdx.x & 31u) | ((wgi & 1u) << 5)) : (threadIdx.x & 63u);
+  const unsigned b = tile * 64u + lane;
+  const unsigned bo = b * 8u, B8 = (unsigned) B * 8u;
+  using IO = TileIO<NS, MemHint<MH>::LA, MemHint<MH>::SA, true>;
+  IO io(st, sto, tile, lane);
+  IO po(pred, pred, tile, lane);   // (only its stores are used)
+  const rsrc_t ri = mkbuf(imu, 7u * B8);
+  const rsrc_t rl = mkbuf(lo, 6u * B8);
+  StepInputs in;
+  if (bc.on & 1) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.gyro[i] = bc.imu[i]; in.accel[i] = bc.imu[3 + i]; }
+    in.dt = bc.imu[6];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.gyro[i] = ldg(ri, i * B8, bo); in.accel[i] = ldg(ri, (3 + i) * B8, bo); }
+    in.dt = ldg(ri, 6u * B8, bo);
+  }
+  if (bc.on & 2) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.z[i] = bc.lo[i]; in.rd[i] = bc.lo[3 + i]; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.z[i] = ldg(rl, i * B8, bo); in.rd[i] = ldg(rl, (3 + i) * B8, bo); }
+  }
+  in.upd = (b < (unsigned) B) && (mask == nullptr || mask[b] != 0);
+  in.qg = qg; in.qa = qa; in.qbg = qbg; in.qba = qba;
+  if (k.qblk != nullptr) {
+    const rsrc_t rq = mkbuf(k.qblk, 4u * B8);
+    in.qg = ldg(rq, 0u, bo); in.qa = ldg(rq, B8, bo); in.qbg = ldg(rq, 2u * B8, bo); in.qba = ldg(rq, 3u * B8, bo);
+  }
+  auto ld = [&io](int comp) { return io.ld(comp); };
+  auto stf = [&io](int comp, double v) { io.st(comp, v); };
+  auto sync = []() { __syncthreads(); };
+  auto xrd = [lane](int s) { return xch[s][lane]; };
+  const PredStore<IO> sp{ &po };
+  if (role == 0) {
+    io.template need<0, Slots<NS>::ROW_SPLIT>();
+    coop_role_core<NS, true, NoCorr, true, false, 0>(ld, stf, [lane](int s, double v) { xch[s][lane] = v; }, xrd, sync, in, k, CorrInputs(), sp);
+  } else {
+    io.template need<Slots<NS>::ROW_SPLIT, Slots<NS>::NROW>();
+    coop_role_passive<NS, true, NoCorr, true>(ld, stf, xrd, sync, in, k, CorrInputs(), sp);
+  }
+}
+
 // The 21-state hot step on FOUR cooperating waves per 64 filters (rbis_quad.hpp): <= 256 registers per role, so two
 // workgroups (8 waves) share a CU and one tile's loads overlap another's arithmetic and stores.  Same inputs, same
 // posterior (to rounding: the c-b coupling enters P_cc as one additive term instead of inside the row operations) and the
@@ -779,6 +847,78 @@ __global__ __launch_bounds__(256, 2) void k_step_quad(const double *st, double *
     const StepInputs in = inputs(false);
     io.template need<SL::QROW[3], SL::QROW[4]>();
     quad_role_passive<UPDATE, 1, 0, true>(ld, stf, xwr, xrd, sync, in, k);
+  }
+}
+
+// k_step_quad<true> that also writes the predicted posterior into `pred` (pb_set_pred_slot; see k_step_coop_pred): roles CB, PW, PA
+// store their predicted rows in front of barrier A, role CC its P_cc behind it (role CB's terms arrive there).  A kernel of its own
+// so that k_step_quad's code object stays what it was; same inputs, same arithmetic, the filtered posterior bit for bit.
+template <int MH = MH_DEFAULT>
+__global__ __launch_bounds__(256, 2) void k_step_quad_pred(const double *st, double *sto, double *pred, int B,
+                                                           const double *__restrict__ imu, const double *__restrict__ lo,
+                                                           const uint8_t *__restrict__ mask, double qg, double qa,
+                                                           double qbg, double qba, Consts k, StepBcast bc)
+{
+  using SL = Slots<21>;
+  using IO = TileIO<21, MemHint<MH>::LA, MemHint<MH>::SA>;
+  __shared__ double xch[Quad::NXCH][64];
+  const int role = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+  const unsigned lane = threadIdx.x & 63u;
+  const unsigned tile = xcd_workgroup(k);
+  const unsigned b = tile * 64u + lane;
+  const unsigned bo = b * 8u, B8 = (unsigned) B * 8u;
+  IO io(st, sto, tile, lane);
+  IO po(pred, pred, tile, lane);   // (only its stores are used)
+  auto inputs = [&](bool meas) {
+    const rsrc_t ri = mkbuf(imu, 7u * B8);
+    const rsrc_t rl = mkbuf(lo, 6u * B8);
+    StepInputs in;
+    if (bc.on & 1) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) { in.gyro[i] = bc.imu[i]; in.accel[i] = bc.imu[3 + i]; }
+      in.dt = bc.imu[6];
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; i++) { in.gyro[i] = ldg(ri, i * B8, bo); in.accel[i] = ldg(ri, (3 + i) * B8, bo); }
+      in.dt = ldg(ri, 6u * B8, bo);
+    }
+    if (bc.on & 2) {
+#pragma unroll
+      for (int i = 0; i < 3; i++) { in.z[i] = bc.lo[i]; in.rd[i] = bc.lo[3 + i]; }
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; i++) { in.z[i] = meas ? ldg(rl, i * B8, bo) : 0.0; in.rd[i] = meas ? ldg(rl, (3 + i) * B8, bo) : 1.0; }
+    }
+    in.upd = (b < (unsigned) B) && (mask == nullptr || mask[b] != 0);
+    in.qg = qg; in.qa = qa; in.qbg = qbg; in.qba = qba;
+    if (k.qblk != nullptr) {
+      const rsrc_t rq = mkbuf(k.qblk, 4u * B8);
+      in.qg = ldg(rq, 0u, bo); in.qa = ldg(rq, B8, bo); in.qbg = ldg(rq, 2u * B8, bo); in.qba = ldg(rq, 3u * B8, bo);
+    }
+    return in;
+  };
+  auto ld = [&io](int comp) { return io.ld(comp); };
+  auto stf = [&io](int comp, double v) { io.st(comp, v); };
+  auto sync = []() { __syncthreads(); };
+  auto xrd = [lane](int s) { return xch[s][lane]; };
+  auto xwr = [lane](int s, double v) { xch[s][lane] = v; };
+  const PredStore<IO> sp{ &po };
+  if (role == 0) {
+    const StepInputs in = inputs(true);
+    io.template need<SL::QROW[0], SL::QROW[1]>();
+    quad_role_cc<true, false, 0, true>(ld, stf, xwr, xrd, sync, in, k, SixIn(), sp);
+  } else if (role == 1) {
+    const StepInputs in = inputs(false);
+    io.template need<SL::QROW[1], SL::QROW[2]>();
+    quad_role_cb<true, 0>(ld, stf, xwr, xrd, sync, in, k, sp);
+  } else if (role == 2) {
+    const StepInputs in = inputs(false);
+    io.template need<SL::QROW[2], SL::QROW[3]>();
+    quad_role_passive<true, 0, 0, true>(ld, stf, xwr, xrd, sync, in, k, SixIn(), sp);
+  } else {
+    const StepInputs in = inputs(false);
+    io.template need<SL::QROW[3], SL::QROW[4]>();
+    quad_role_passive<true, 1, 0, true>(ld, stf, xwr, xrd, sync, in, k, SixIn(), sp);
   }
 }
 

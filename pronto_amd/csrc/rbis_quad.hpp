@@ -79,10 +79,12 @@ PB_HD void fcc_apply(const ProcBlocks &f, double (&V)[9], double (&Cc)[9], doubl
 //      P'(:, omega) behind barrier A, then the velocity block runs on the result -- no extra barrier
 //   2  the velocity block, then the position block on its posterior: barrier B2 (every role has consumed the first hand-off, whose
 //      slots the second one re-uses) and barrier C (role CC has published the second factors)
-template <bool UPDATE, bool LEG = false, int SIX = 0, bool PIN = true, class LD, class ST, class XW, class XR, class SYNC>
-PB_HD void quad_role_cc(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k, const SixIn &six = SixIn())
+// SP: the predicted rows (k_step_quad_pred; see NoPredStore, rbis_coop.hpp) -- the plain fused step only
+template <bool UPDATE, bool LEG = false, int SIX = 0, bool PIN = true, class LD, class ST, class XW, class XR, class SYNC, class SP = NoPredStore>
+PB_HD void quad_role_cc(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k, const SixIn &six = SixIn(), SP sp = SP())
 {
   static_assert(SIX == 0 || UPDATE, "the six-row leg-odometry modes ride on the velocity update");
+  static_assert(!SP::on || (UPDATE && !LEG && SIX == 0), "the predicted rows: the plain fused step only");
   constexpr int NS = 21;
   using L = Lay<NS>;
   double x[NS], q[4];
@@ -181,6 +183,13 @@ PB_HD void quad_role_cc(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs 
       Pc[pk(3 + r, c)] += xr(Quad::X_H2 + 3 * r + c);
       if (c <= r) Pc[pk(3 + r, 3 + c)] += xr(Quad::X_H2 + 9 + pk(r, c));
     }
+  if constexpr (SP::on) {  // the predicted P_cc (final only now: role CB's terms arrive behind barrier A) and the log-likelihood
+#pragma unroll
+    for (int i = 0; i < 9; i++)
+#pragma unroll
+      for (int j = 0; j <= i; j++) sp(L::OFF_P + pk(core_full(i), core_full(j)), Pc[pk(i, j)]);
+    sp(L::OFF_LL, ll);
+  }
   if constexpr (SIX == 1) {  // the angular-velocity block: P_cc -= A A^T / d with A = P'(c, omega) from role PW
     const double idw = xr(Quad::X6_ID);
     ll += xr(Quad::X6_LLI);
@@ -338,9 +347,10 @@ PB_HD void quad_role_cc(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs 
 // ------------------------------------------------------------------------------------------------------------
 // wave 1, role CB: P_cb, P_bb, x[bg ba], x[omega]
 // ------------------------------------------------------------------------------------------------------------
-template <bool UPDATE, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC>
-PB_HD void quad_role_cb(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k)
+template <bool UPDATE, int SIX = 0, class LD, class ST, class XW, class XR, class SYNC, class SP = NoPredStore>
+PB_HD void quad_role_cb(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k, SP sp = SP())
 {
+  static_assert(!SP::on || (UPDATE && SIX == 0), "the predicted rows: the plain fused step only");
   constexpr int NS = 21;
   using L = Lay<NS>;
   double x[NS], q[4];
@@ -427,6 +437,19 @@ PB_HD void quad_role_cb(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs 
   for (int r = 0; r < 3; r++) {
     Pbb[pk(r, r)] += in.qbg * in.dt;
     Pbb[pk(3 + r, 3 + r)] += in.qba * in.dt;
+  }
+  if constexpr (SP::on) {  // the predicted P_cb, P_bb, x[bg ba], x[omega]
+#pragma unroll
+    for (int j = 0; j < 6; j++) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) sp(L::OFF_P + pk(core_full(9 + j), core_full(i)), Y[i / 3][j / 3][3 * (i % 3) + j % 3]);
+#pragma unroll
+      for (int j2 = 0; j2 <= j; j2++) sp(L::OFF_P + pk(core_full(9 + j), core_full(9 + j2)), Pbb[pk(j, j2)]);
+    }
+#pragma unroll
+    for (int i = 0; i < 6; i++) sp(L::OFF_VEC + 15 + i, xb[i]);
+#pragma unroll
+    for (int i = 0; i < 3; i++) sp(L::OFF_VEC + i, xw_[i]);
   }
   sync();  // A
   if constexpr (SIX == 1) {
@@ -575,9 +598,11 @@ PB_HD void quad_role_cb(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs 
 // ------------------------------------------------------------------------------------------------------------
 // PIN: the panel propagation is finished in FRONT of barrier A (pb_pin, rbis_coop.hpp) -- the plain step gains 0.8 us of 40 at 64k
 // filters; the pair kernels, whose role PW runs the odometry first, lose 1-2 us with it and leave the order to the compiler.
-template <bool UPDATE, int J, int SIX = 0, bool PIN = false, class LD, class ST, class XW, class XR, class SYNC>
-PB_HD void quad_role_passive(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k, const SixIn &six = SixIn())
+template <bool UPDATE, int J, int SIX = 0, bool PIN = false, class LD, class ST, class XW, class XR, class SYNC, class SP = NoPredStore>
+PB_HD void quad_role_passive(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k, const SixIn &six = SixIn(),
+                             SP sp = SP())
 {
+  static_assert(!SP::on || (UPDATE && SIX == 0), "the predicted rows: the plain fused step only");
   constexpr int NS = 21;
   using L = Lay<NS>;
   double x[NS], q[4];
@@ -680,6 +705,32 @@ PB_HD void quad_role_passive(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepIn
     for (int sb = 0; sb < 5; sb++)
 #pragma unroll
       for (int i = 0; i < 9; i++) pb_pin(X[sb][i]);
+  }
+  if constexpr (SP::on) {  // the predicted panel J, P_JJ (+ P(accel, omega)), and x[v chi Delta] + quat (J == 0) / x[accel] (J == 1)
+#pragma unroll
+    for (int sb = 0; sb < 5; sb++)
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) sp(L::OFF_P + pk(core_full(3 * sb + r), passive_full(3 * J + c)), X[sb][3 * r + c]);
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+      if constexpr (J == 1) {
+#pragma unroll
+        for (int c = 0; c < 3; c++) sp(L::OFF_P + pk(passive_full(3 + r), passive_full(c)), Paw[3 * r + c]);
+      }
+#pragma unroll
+      for (int c = 0; c <= r; c++) sp(L::OFF_P + pk(passive_full(3 * J + r), passive_full(3 * J + c)), Pjj[pk(r, c)]);
+    }
+    if constexpr (J == 0) {
+#pragma unroll
+      for (int i = 0; i < 9; i++) sp(L::OFF_VEC + core_full(i), x[core_full(i)]);
+#pragma unroll
+      for (int i = 0; i < 4; i++) sp(L::OFF_QUAT + i, q[i]);
+    } else {
+#pragma unroll
+      for (int i = 0; i < 3; i++) sp(L::OFF_VEC + passive_full(3 + i), xp[i]);
+    }
   }
   sync();  // A
   if constexpr (SIX == 1 && J == 1) {

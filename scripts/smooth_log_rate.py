@@ -1,6 +1,7 @@
 """Whole-log RTS smoothing with bounded memory (pb_smooth_log: checkpoint and recompute): device time per smoothed filter-step,
-forward pass + recompute + smoother steps, and the slots it took against the 2 T a posterior per update would need.
-  python scripts/smooth_log_rate.py            env: SMOOTH_LOG_CASES="n,B,T,K;..." """
+forward pass + recompute + smoother steps, and the slots it took against the 2 T a posterior per update would need.  With
+SMOOTH_LOG_FUSED=1 every case is timed a second time on pb_smooth_log_fused (one fused launch per step) in the same run.
+  python scripts/smooth_log_rate.py            env: SMOOTH_LOG_CASES="n,B,T,K;..."  SMOOTH_LOG_FUSED=0|1 """
 import os
 import sys
 
@@ -21,13 +22,16 @@ for case in cases.split(";"):
     est.reset(vec, quat, P0)
     need = est.smooth_log_slots(T, K)
     est.history_reserve(need)
-    est.smooth_log(imu[:2 * K], lo[:2 * K], mask[:2 * K], q4, 1e-3, K)   # warm-up
-    est.reset(vec, quat, P0)
-    ms = est.smooth_log(imu, lo, mask, q4, 1e-3, K, timed=True)
-    per_slot = (n + 5 + n * (n + 1) // 2) * 8 * B / 1e6
-    s = est.summary()
-    print("pb_smooth_log n=%d: %d steps x %d filters, stride %d: %d slots (%.1f GB; a posterior per update: %d slots, %.0f GB): %.1f ms = %.2f us per "
-          "smoothed step of the batch = %.4f us per smoothed filter-step; nonfinite %d"
-          % (n, T, B, K, need, need * per_slot / 1e3, 2 * T, 2 * T * per_slot / 1e3, ms, ms * 1e3 / T, ms * 1e3 / (T * B), int(s[3])), flush=True)
+    for fused in ((False, True) if os.environ.get("SMOOTH_LOG_FUSED", "0") == "1" else (False,)):
+        est.reset(vec, quat, P0)
+        est.smooth_log(imu[:2 * K], lo[:2 * K], mask[:2 * K], q4, 1e-3, K, fused=fused)   # warm-up
+        est.reset(vec, quat, P0)
+        ms = est.smooth_log(imu, lo, mask, q4, 1e-3, K, timed=True, fused=fused)
+        per_slot = (n + 5 + n * (n + 1) // 2) * 8 * B / 1e6
+        s = est.summary()
+        print("%s n=%d: %d steps x %d filters, stride %d: %d slots (%.1f GB; a posterior per update: %d slots, %.0f GB): %.1f ms = %.2f us per "
+              "smoothed step of the batch = %.4f us per smoothed filter-step; nonfinite %d"
+              % ("pb_smooth_log_fused" if fused else "pb_smooth_log", n, T, B, K, need, need * per_slot / 1e3, 2 * T, 2 * T * per_slot / 1e3, ms,
+                 ms * 1e3 / T, ms * 1e3 / (T * B), int(s[3])), flush=True)
     est.close()
     del imu, lo, mask
