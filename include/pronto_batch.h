@@ -462,6 +462,26 @@ int pb_state_restore(pb_ctx *ctx, int slot);   /* head posterior <- slot */
  * =reg the kernel of rounds 2-4 (16 / 32 lanes per filter); PRONTO_SMOOTH_PIVOT=1 that kernel with Eigen's pivoting. */
 int pb_smooth_step(pb_ctx *ctx, int slot_next_pred, int slot_next, int slot_cur, int slot_out, double dt);
 
+/* Per-filter selection between two posteriors: dst <- src for the filters whose mask entry equals `when` (0 or 1; a non-zero entry
+ * counts as 1); every other filter's column of dst is left untouched, bit for bit.  dst / src: checkpoint slots, or PB_SLOT_HEAD = the
+ * head posterior (the array it currently lives in: the context's own, or the checkpoint slot an update wrote it into).  Copies every
+ * per-filter field of the state array (vec, quat, loglik, packed P).  mask [B]: PB_HOST or PB_DEVICE.  dst == src: no-op.
+ * One launch (pb_select.hip): a lane per filter, 16-byte accesses; a filter that is not selected costs its mask byte only.
+ * PB_ERR_STATE: a slot out of range (or the head before pb_reset); PB_ERR_ARG: NULL mask, `when` not 0 / 1, `mem` not PB_HOST /
+ * PB_DEVICE.  SegmentBatcher (segment_batcher.hpp) keeps every segment's posterior at the end of its own log with it. */
+#define PB_SLOT_HEAD (-1)
+int pb_slot_select(pb_ctx *ctx, int dst, int src, const uint8_t *mask, int when, int mem);
+/* pb_smooth_step for the filters with step[b] = 1; for step[b] = 0 slot_out <- slot_next bit for bit (the filter had no INS update at
+ * k+1: its smoothed posterior at k IS its smoothed posterior at k+1).  step: PB_HOST or PB_DEVICE; NULL = all (exactly pb_smooth_step).
+ * Why carrying "next" is right: for a filter whose log segment has no INS update at global step k+1, nothing happened to it between
+ * k and k+1, so its filtered posterior at k+1 is its filtered posterior at k.  When it has a real update later, at k+2 say, the global
+ * step k+1 smooths with cur = posterior(k+1) = posterior(k), predicted = its INS update at k+2 and next = smoothed(k+2): exactly the
+ * reference's step from ITS k to ITS next update.  So the carried value, held over the idle ticks, is that filter's correctly smoothed
+ * posterior at its own step; an idle tick at the end of its log carries the posterior it ended with (the newest step's "next").
+ * pb_smooth_step then pb_slot_select(slot_out, slot_next, step, 0), on the same stream; the smoother kernels are not changed. */
+int pb_smooth_step_masked(pb_ctx *ctx, int slot_next_pred, int slot_next, int slot_cur, int slot_out, double dt, const uint8_t *step,
+                          int mem);
+
 /* EKFSmoothBackwardsPass over a WHOLE log with bounded memory (mav_state_est.cpp:98-189, lcm_front_end.cpp:168-203: the reference's
  * "-S" smooths the entire log; it keeps three posteriors per step by value, which for a batch is 2 T slots of the whole state).
  * Checkpoint and recompute: the forward pass filters the n_steps steps of the streams (as pb_run_legodo takes them; per step the

@@ -17,6 +17,7 @@ PB_OK, PB_ERR_ARG, PB_ERR_HIP, PB_ERR_NO_DEVICE, PB_ERR_STATE = range(5)
 PB_HOST, PB_DEVICE, PB_HOST_BROADCAST = 0, 1, 2
 PB_R_DIAG_BROADCAST, PB_R_DIAG, PB_R_FULL = 0, 1, 2
 PB_CORR_POS_ORIENT, PB_CORR_POS_YAW = 0, 1
+PB_SLOT_HEAD = -1
 
 
 def sources():
@@ -131,6 +132,8 @@ _SIGS = {
     "pb_host_free": (C.c_int, [C.c_void_p, C.c_void_p]),
     "pb_state_restore": (C.c_int, [C.c_void_p, C.c_int]),
     "pb_smooth_step": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double]),
+    "pb_smooth_step_masked": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_int]),
+    "pb_slot_select": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]),
     "pb_get_head": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_get_filter_state": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "pb_summary": (C.c_int, [C.c_void_p, _dp]),

@@ -144,6 +144,17 @@ class BatchEstimator:
     def smooth_step(self, slot_next_pred, slot_next, slot_cur, slot_out, dt):
         self._chk(self._L.pb_smooth_step(self._h, slot_next_pred, slot_next, slot_cur, slot_out, dt))
 
+    def smooth_step_masked(self, slot_next_pred, slot_next, slot_cur, slot_out, dt, step=None):
+        """pb_smooth_step for the filters with step[b] = 1; slot_out <- slot_next for step[b] = 0.  step: [B] uint8 (numpy or a
+        device tensor) or None (= every filter)."""
+        p, m = _ptr(step, np.uint8, shape=(self.B,))
+        self._chk(self._L.pb_smooth_step_masked(self._h, slot_next_pred, slot_next, slot_cur, slot_out, dt, p, PB_HOST if m is None else m))
+
+    def slot_select(self, dst, src, mask, when=1):
+        """dst <- src for the filters whose mask entry equals `when` (0 / 1); dst / src: checkpoint slots or _lib.PB_SLOT_HEAD."""
+        p, m = _ptr(mask, np.uint8, shape=(self.B,))
+        self._chk(self._L.pb_slot_select(self._h, int(dst), int(src), p, int(when), PB_HOST if m is None else m))
+
     def smooth_log_slots(self, n_steps, stride):
         return self._L.pb_smooth_log_slots(n_steps, stride)
 

@@ -282,6 +282,17 @@ public:
   // NULL for it).  Whoever takes this step hands the mask to the library first (announce): the step is then a no-op for it.
   const uint8_t *valid_dev = nullptr;
   void announce(pb_ctx *ctx) const { if (valid_dev) pb_set_imu_valid(ctx, valid_dev); }
+  // the same mask of a step built from HOST messages (InsHandler::build: such a filter's block entry has dt = 0), an owned copy for as
+  // long as the step lives in the history: EKFSmoothBackwardsPass reads it (the step itself never announces it)
+  std::vector<uint8_t> valid_host;
+  // some filter MAY have no message in this step: its mask has a zero, or it lives on the device and was never seen on the host
+  bool may_idle = false;
+  // this step's mask and where it lives (PB_HOST / PB_DEVICE); NULL = every filter has a message
+  const uint8_t *stepMask(int &mem) const
+  {
+    mem = valid_host.empty() ? PB_DEVICE : PB_HOST;
+    return valid_host.empty() ? valid_dev : valid_host.data();
+  }
   BatchArray imu_block;
   double q_gyro, q_accel, q_gyro_bias, q_accel_bias;
   // set by MavStateEstimator when this step last ran fused with the update behind it (fuse_ins_legodo): its own posterior then has no
@@ -865,7 +876,46 @@ public:
   // into an existing checkpoint: when the partner has one, into one more window slot.
   int64_t smoother_reapplied_updates = 0;   // statistics: updates re-applied to re-derive posteriors that had no checkpoint
   int64_t smoother_reapplied_pairs = 0;     // ... of which fused INS + leg-odometry pairs, re-applied as one launch (each counts once)
+  int64_t smoother_masked_steps = 0;        // smoother steps that also ran pb_slot_select (ragged overload: a tick some filter sat out)
   int EKFSmoothBackwardsPass(double dt, const std::function<void(int64_t, int)> &on_smoothed)
+  {
+    return smooth_pass(dt, -1, false, [&](int64_t utime, int slot, const uint8_t *, int) {
+      if (on_smoothed) on_smoothed(utime, slot);
+    });
+  }
+  // The same pass for a batch of INDEPENDENT log segments (SegmentBatcher): a filter need not have an INS update at every step.  Step j
+  // runs pb_smooth_step_masked with the mask of INS update j+1 (RBISIMUProcessStep::stepMask): a filter without a message there keeps
+  // the smoothed posterior of step j+1, which is its smoothed posterior at its own step (pronto_batch.h).  A step whose mask has no zero
+  // -- known on the host for masks that came from the host, may_idle -- runs plain pb_smooth_step, with no select launch; with no mask in
+  // the window the smoothed posteriors are bit for bit those of the two-argument pass.  smoother_masked_steps counts the select launches.
+  // terminal_slot >= 0 (a slot taken out of the pool with reserveSlot): "next" of the newest step instead of the head -- every filter's
+  // posterior at the end of ITS log, where the head of a filter whose segment ended early is not (its idle steps re-derive its angular
+  // velocity / acceleration entries).  on_smoothed(utime of INS_j, slot, valid, valid_mem): valid = INS update j's mask, NULL when it has
+  // none; valid_mem = where it lives (stepMask): PB_HOST for a step built from host messages, PB_DEVICE for one built on the device.
+  int EKFSmoothBackwardsPass(double dt, int terminal_slot,
+                             const std::function<void(int64_t utime, int slot, const uint8_t *valid, int valid_mem)> &on_smoothed)
+  {
+    if (terminal_slot >= history_slots || (terminal_slot >= 0 && std::find(free_slots.begin(), free_slots.end(), terminal_slot) != free_slots.end())) {
+      fprintf(stderr, "EKFSmoothBackwardsPass: terminal slot %d is not a slot taken with reserveSlot()\n", terminal_slot);
+      return -1;
+    }
+    return smooth_pass(dt, terminal_slot, true, on_smoothed);
+  }
+  // a checkpoint slot taken out of the pool for the caller (the history never recycles it); -1 = none is free.  releaseSlot gives it back.
+  int reserveSlot()
+  {
+    if (free_slots.empty()) return -1;
+    const int slot = free_slots.back();
+    free_slots.pop_back();
+    return slot;
+  }
+  void releaseSlot(int slot)
+  {
+    if (slot >= 0 && slot < history_slots && std::find(free_slots.begin(), free_slots.end(), slot) == free_slots.end()) free_slots.push_back(slot);
+  }
+
+private:
+  int smooth_pass(double dt, int terminal_slot, bool masked, const std::function<void(int64_t, int, const uint8_t *, int)> &on_smoothed)
   {
     auto &map = history.updateMap;
     flushPending();
@@ -904,9 +954,15 @@ public:
     const int head_keep = (maxgap > 0 || head_loose) ? free_slots[nf - 3] : -1;
     auto W = [&](int i) { return free_slots[nf - 4 - (size_t) i]; };   // window slots
     int rc = PB_OK;
+    bool head_saved = false;
+    // an error leaves no output / predicted slot pending and the newest posterior as the head (re-applied updates may have moved it)
     auto bail = [&](const char *what) {
       last_status = rc;
       fprintf(stderr, "EKFSmoothBackwardsPass: %s: %s\n", what, pb_last_error(ctx));
+      pb_set_pred_slot(ctx, -1);
+      pb_set_output_slot(ctx, -1);
+      if (head_saved && pb_state_restore(ctx, head_keep) == PB_OK) pb_set_utime(ctx, head_utime);
+      device_head = nullptr;
       return -1;
     };
     if (head_keep >= 0) {
@@ -915,8 +971,9 @@ public:
         return -1;
       }
       if ((rc = pb_state_save(ctx, head_keep)) != PB_OK) return bail("saving the head");
+      head_saved = true;
     }
-    int next = head_loose ? head_keep : seq.back().second, steps = 0, toggle = 0;
+    int next = terminal_slot >= 0 ? terminal_slot : (head_loose ? head_keep : seq.back().second), steps = 0, toggle = 0;
     int j = (int) ins.size() - 2;   // the step being smoothed: needs the posteriors of updates ins[j+1] - 1 and ins[j+1]
     // stretches (a, e]: a = a checkpointed update, e = the next checkpointed update (or the newest update)
     for (int m = (int) cks.size() - 1; m >= 0 && j >= 0; m--) {
@@ -951,8 +1008,23 @@ public:
       while (j >= 0 && ins[(size_t) j + 1] > a) {
         const int ip = ins[(size_t) j + 1];
         const int out = spare[toggle];
-        if ((rc = pb_smooth_step(ctx, slot_at(ip), next, slot_at(ip - 1), out, dt)) != PB_OK) return bail("smoother step");
-        if (on_smoothed) on_smoothed(seq[(size_t) ins[(size_t) j]].first->utime, out);
+        int step_mem = PB_DEVICE;
+        const uint8_t *step = nullptr;
+        if (masked)
+          if (auto *nx = dynamic_cast<const RBISIMUProcessStep *>(seq[(size_t) ip].first))
+            if (nx->may_idle) step = nx->stepMask(step_mem);
+        if (step != nullptr) {
+          if ((rc = pb_smooth_step_masked(ctx, slot_at(ip), next, slot_at(ip - 1), out, dt, step, step_mem)) != PB_OK) return bail("smoother step");
+          smoother_masked_steps++;
+        } else if ((rc = pb_smooth_step(ctx, slot_at(ip), next, slot_at(ip - 1), out, dt)) != PB_OK) {
+          return bail("smoother step");
+        }
+        if (on_smoothed) {
+          int cur_mem = PB_DEVICE;
+          const auto *cu = dynamic_cast<const RBISIMUProcessStep *>(seq[(size_t) ins[(size_t) j]].first);
+          const uint8_t *cur_valid = cu != nullptr ? cu->stepMask(cur_mem) : nullptr;
+          on_smoothed(seq[(size_t) ins[(size_t) j]].first->utime, out, cur_valid, cur_mem);
+        }
         next = out;
         toggle ^= 1;
         steps++;
@@ -967,7 +1039,6 @@ public:
     return steps;
   }
 
-private:
   bool flushing_ = false;
   int holding_ = 0;  // updates at the end of the history that have not been applied yet (0, 1 = an INS step, 2 = INS + legodo)
   // an INS step followed by the velocity measurement LegOdoCommon's lin_rate mode produces (what run_fused accepts)
@@ -1658,6 +1729,7 @@ private:
     auto *u = new RBISIMUProcessStep(BatchArray((const double *) blk, PB_DEVICE), cov_gyro, cov_accel, cov_gyro_bias, cov_accel_bias, utime);
     u->owned_dev = std::make_shared<DeviceBlock>(ins_pool_, blk);
     u->valid_dev = mask_out;
+    u->may_idle = mask_out != nullptr && (mem != PB_HOST || std::find(valid, valid + est->B, (uint8_t) 0) != valid + est->B);
     return u;
   }
   // valid [B] (per-filter host messages only): a filter without a message takes its step with dt = 0 -- with the sample it was
@@ -1694,7 +1766,12 @@ private:
       }
       blk[(size_t) 6 * B + b] = (valid != nullptr && mem == PB_HOST && !valid[b]) ? 0.0 : dt_;
     }
-    return new RBISIMUProcessStep(std::move(blk), cov_gyro, cov_accel, cov_gyro_bias, cov_accel_bias, utime, mem);
+    auto *u = new RBISIMUProcessStep(std::move(blk), cov_gyro, cov_accel, cov_gyro_bias, cov_accel_bias, utime, mem);
+    if (valid != nullptr && mem == PB_HOST) {
+      u->valid_host.assign(valid, valid + B);
+      u->may_idle = std::find(valid, valid + B, (uint8_t) 0) != valid + B;
+    }
+    return u;
   }
 };
 

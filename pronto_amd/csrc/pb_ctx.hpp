@@ -188,3 +188,5 @@ int pbk_update_ct(pb_ctx *c, int m, const int *idx, const double *z, const doubl
 // pb_smooth.hip
 int pbk_smooth_step(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);
 int pbk_smooth_wide(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);   // 15 states (pb_smooth_wide.hip)
+// pb_select.hip: dst <- src for the filters whose mask_dev entry (device, [B]; non-zero counts as 1) equals `when`, every other column untouched
+int pbk_slot_select(pb_ctx *c, double *dst, const double *src, const uint8_t *mask_dev, int when);

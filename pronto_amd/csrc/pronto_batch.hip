@@ -594,8 +594,10 @@ extern "C" int pb_step_legodo(pb_ctx *c, const double *imu_block, const double *
 extern "C" int pb_step_legodo_split(pb_ctx *c, const double *imu_block, int imu_mem, const double *lo_block,
                                     const uint8_t *mask, int lo_mem, const double q[4])
 {
+  // (the same space: pb_step_legodo takes the pb_set_imu_valid mask and a predicted slot itself -- hand the call on BEFORE taking the
+  // mask here, or its own ImuIdleTake would find it gone)
+  if (imu_mem == lo_mem) return pb_step_legodo(c, imu_block, lo_block, mask, q, imu_mem);
   ImuIdleTake idle(c);
-  if (imu_mem == lo_mem) return pb_step_legodo(c, imu_block, lo_block, mask, q, imu_mem);   // (which consumes a predicted slot)
   PredTake pred(c);
   ENTER(c);
   NEED_STATE(c);
@@ -1899,6 +1901,34 @@ extern "C" int pb_smooth_step(pb_ctx *c, int slot_next_pred, int slot_next, int 
   const double *cu = c->hist + (size_t) slot_cur * n;
   double *out = c->hist + (size_t) slot_out * n;
   return pbk_smooth_step(c, np_, ns_, cu, out, dt);
+}
+
+// ---- per-filter selection between posteriors (independent log segments of different lengths) ----
+extern "C" int pb_slot_select(pb_ctx *c, int dst, int src, const uint8_t *mask, int when, int mem)
+{
+  ENTER(c);
+  for (int sl : { dst, src })
+    if (sl < PB_SLOT_HEAD || sl >= c->nhist) return fail(c, PB_ERR_STATE, "pb_slot_select: checkpoint slot %d of %d", sl, c->nhist);
+  if (!mask) return fail(c, PB_ERR_ARG, "pb_slot_select: NULL mask");
+  if (when != 0 && when != 1) return fail(c, PB_ERR_ARG, "pb_slot_select: when = %d (0 or 1)", when);
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_slot_select: mem must be PB_HOST or PB_DEVICE");
+  if ((dst == PB_SLOT_HEAD || src == PB_SLOT_HEAD) && !c->have_state) return fail(c, PB_ERR_STATE, "pb_slot_select: the head before pb_reset");
+  const size_t n = c->state_doubles;
+  double *d = dst == PB_SLOT_HEAD ? c->st : c->hist + (size_t) dst * n;
+  const double *s = src == PB_SLOT_HEAD ? c->st : c->hist + (size_t) src * n;
+  if (d == s) return PB_OK;
+  Part p[1] = { { mask, (size_t) c->B, 0 } };
+  int rc = stage_in(c, mem, p, 1);
+  if (rc) return rc;
+  return pbk_slot_select(c, d, s, (const uint8_t *) p[0].dev, when);
+}
+
+extern "C" int pb_smooth_step_masked(pb_ctx *c, int slot_next_pred, int slot_next, int slot_cur, int slot_out, double dt, const uint8_t *step,
+                                     int mem)
+{
+  if (int rc = pb_smooth_step(c, slot_next_pred, slot_next, slot_cur, slot_out, dt)) return rc;
+  if (!step) return PB_OK;
+  return pb_slot_select(c, slot_out, slot_next, step, 0, mem);   // (slot_out != slot_next: pb_smooth_step checked it)
 }
 
 // ---- whole-log RTS smoothing with bounded memory: checkpoint and recompute ----

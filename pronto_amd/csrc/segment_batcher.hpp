@@ -27,6 +27,18 @@
 // filter idles in the batch afterwards; an idle step keeps pose, velocity, biases and covariance but re-derives the
 // angular-velocity / acceleration entries from its last sample, so the estimator's own head is NOT the result of a finished run.
 //
+// Smoothing.  enableSmoothing() before run() makes the batch the reference's "-S" run of every log (lcm_front_end.cpp:168-203,
+// mav_state_est.cpp:98-189): a checkpoint slot is taken out of the estimator's pool for the TERMINAL posteriors, and finalize() copies
+// the head of the segments that end into it (pb_slot_select, on the device), so that it holds every segment's posterior at the end of
+// its own log.  The batcher also keeps every batched IMU message's per-segment validity and time on the host.  smooth(dt, sink) then
+// runs the estimator's ragged-aware EKFSmoothBackwardsPass (terminal slot as the newest step's "next", pb_smooth_step_masked on the
+// ticks some segment sat out) and calls sink(step, slot, emit, utimes) once per batched IMU message, newest first: `slot` holds the
+// smoothed posteriors of that tick until the next call; emit[s] = 1 exactly where it is one of segment s's smoothed posteriors -- s had
+// an INS update at this tick and has a later one in the history -- so segment s receives its own INS update count - 1 of them, newest
+// first, as a single-segment pass over its log would; utimes[s] = segment s's own message time; step = the index of this IMU message in
+// every segment's own log (messages are aligned by index per channel).  The history must keep the whole log (utime_history_span,
+// history_slots).  INS updates are matched to batched IMU messages by batch time; smooth() returns -1 when two messages share one.
+//
 // Host side only; every batched array lives in page-locked memory (pb_host_alloc) so that the library's double-buffered staging
 // copies run as DMA.  Decoding goes through the run-time .lcm schema (lcm_schema.hpp): the bot_core definitions are the caller's.
 #pragma once
@@ -65,6 +77,7 @@ public:
   {
     est_->flushPending();   // (an update the estimator is holding back may still read the device blocks)
     pb_sync(est_->ctx);
+    if (terminal_ >= 0) est_->releaseSlot(terminal_);
     for (void *p : pinned_) pb_host_free(est_->ctx, p);
     for (void *p : device_) pb_free(est_->ctx, p);
   }
@@ -88,6 +101,72 @@ public:
     return true;
   }
   int segments() const { return (int) segs_.size(); }
+
+  // Before run(): keep what smooth() needs (see the head of this file).  false: the estimator has no free checkpoint slot.
+  bool enableSmoothing()
+  {
+    if (terminal_ >= 0) return true;
+    est_->flushPending();
+    terminal_ = est_->reserveSlot();
+    if (terminal_ < 0) {
+      fprintf(stderr, "SegmentBatcher::enableSmoothing: no free checkpoint slot (state_estimator.history_slots)\n");
+      return false;
+    }
+    // (every column holds a posterior from the start: a segment never added, or one that never ends, keeps its initial state)
+    if (pb_state_save(est_->ctx, terminal_) != PB_OK) {
+      fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
+      est_->releaseSlot(terminal_);
+      terminal_ = -1;
+      return false;
+    }
+    return true;
+  }
+  // The smoothed posteriors of every segment, newest first (see the head of this file).  Returns the number of sink calls (batched IMU
+  // messages smoothed), -1 on an error (smoothing not enabled, or the estimator's pass failed).
+  int smooth(double dt, std::function<void(int segment_step_base, int slot, const uint8_t *emit_host, const int64_t *utime_host)> sink)
+  {
+    if (terminal_ < 0) {
+      fprintf(stderr, "SegmentBatcher::smooth: enableSmoothing() was not called before run()\n");
+      return -1;
+    }
+    if (terminal_failed_) {
+      fprintf(stderr, "SegmentBatcher::smooth: a segment's final posterior could not be kept (see the error of finalize)\n");
+      return -1;
+    }
+    est_->flushPending();
+    // batched IMU message by its batch-level time (one message per time: the pass names an INS update by its time)
+    std::map<int64_t, int> tick_of;
+    for (int t = 0; t < (int) imu_tick_utime_.size(); t++)
+      if (!tick_of.emplace(imu_tick_utime_[(size_t) t], t).second) {
+        fprintf(stderr, "SegmentBatcher::smooth: two batched IMU messages at batch time %lld\n", (long long) imu_tick_utime_[(size_t) t]);
+        return -1;
+      }
+    // each segment's last INS UPDATE in the history (the handler may have made no step of an IMU message: downsampling)
+    std::vector<int> last((size_t) B_, -1);
+    for (auto u = est_->history.updateMap.begin(); u != est_->unprocessed_updates_start; ++u) {
+      if (u->second->sensor_id != RBISUpdateInterface::ins) continue;
+      auto it = tick_of.find(u->first);
+      if (it == tick_of.end()) {
+        fprintf(stderr, "SegmentBatcher::smooth: an INS update at %lld that no batched IMU message made\n", (long long) u->first);
+        return -1;
+      }
+      for (int s = 0; s < B_; s++)
+        if (imu_valid_[(size_t) it->second * B_ + s]) last[(size_t) s] = std::max(last[(size_t) s], it->second);
+    }
+    std::vector<uint8_t> emit((size_t) B_, 0);
+    int calls = 0;
+    bool lost = false;
+    const int steps = est_->EKFSmoothBackwardsPass(dt, terminal_, [&](int64_t utime, int slot, const uint8_t *, int) {
+      auto it = tick_of.find(utime);   // (found: every INS update of the history was matched above)
+      const int t = it == tick_of.end() ? -1 : it->second;
+      lost = lost || t < 0;
+      if (t < 0) return;
+      for (int s = 0; s < B_; s++) emit[(size_t) s] = imu_valid_[(size_t) t * B_ + s] && t < last[(size_t) s];
+      sink(t, slot, emit.data(), &imu_utime_[(size_t) t * B_]);
+      calls++;
+    });
+    return steps < 0 || lost ? -1 : calls;
+  }
 
   // ---- typed subscriptions: channel -> the callback FrontEnd::addSensor returned ----
   // bot_core::ins_t by field name (utime, gyro[3], accel[3]): InsHandler::processMessage
@@ -119,6 +198,7 @@ public:
       }
       msgs::ins_t m{ utime, BatchArray(blk, PB_HOST), BatchArray(blk + (size_t) 3 * B_, PB_HOST) };
       m.valid = valid;
+      keep_imu_tick(col, valid, utime);
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
@@ -204,6 +284,7 @@ public:
       m.raw_dt = raw_dt;
       m.utimes = ut;
       m.mem = PB_HOST;
+      keep_imu_tick(col, valid, utime);
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
@@ -594,11 +675,27 @@ private:
     sg.order.erase(it);
     return true;
   }
+  // smoothing: one batched IMU message's per-segment validity and message times (the handler gets the same mask)
+  void keep_imu_tick(const std::vector<const Rec *> &col, const uint8_t *valid, int64_t utime)
+  {
+    if (terminal_ < 0) return;
+    imu_tick_utime_.push_back(utime);
+    imu_valid_.insert(imu_valid_.end(), valid, valid + B_);
+    for (int s = 0; s < B_; s++) imu_utime_.push_back(col[(size_t) s] ? col[(size_t) s]->utime : 0);
+  }
   // the runs of segments [first, first + count) are complete: read their heads (applies whatever the estimator holds back first)
   void finalize(int first, int count)
   {
     const int n = est_->n;
     est_->flushPending();
+    if (terminal_ >= 0) {   // smoothing: their posteriors at the end of their own logs, kept on the device (the newest step's "next")
+      ending_.assign((size_t) B_, 0);
+      std::fill_n(ending_.begin() + first, count, (uint8_t) 1);
+      if (pb_slot_select(est_->ctx, terminal_, PB_SLOT_HEAD, ending_.data(), 1, PB_HOST) != PB_OK) {
+        fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
+        terminal_failed_ = true;   // (smooth() refuses: the terminal slot does not hold these segments' results)
+      }
+    }
     std::vector<double> v((size_t) n * count), q((size_t) 4 * count), c((size_t) n * n * count), l((size_t) count);
     if (pb_get_head(est_->ctx, first, count, v.data(), q.data(), c.data(), l.data(), PB_HOST) != PB_OK) {
       fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
@@ -639,6 +736,12 @@ private:
   std::vector<std::string> chan_names_;
   int first_alive_ = 0;
   std::vector<void *> pinned_, device_;
+  int terminal_ = -1;                    // enableSmoothing: the estimator's checkpoint slot of the terminal posteriors
+  bool terminal_failed_ = false;         // a copy into it failed
+  std::vector<int64_t> imu_tick_utime_;  // per batched IMU message: its batch-level time ...
+  std::vector<uint8_t> imu_valid_;       // ... [B] which segments had a message ...
+  std::vector<int64_t> imu_utime_;       // ... [B] and their own message times
+  std::vector<uint8_t> ending_;
 };
 
 }  // namespace MavStateEst
