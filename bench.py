@@ -11,9 +11,13 @@ GPUs); the line's "scaling" and config.workload say which one ran.  `python benc
 touches the GPU); under torch.distributed.run (WORLD_SIZE set) it is one of the ranks.
 
 The timed region is exactly --steps launches (`timed_steps`), after --warmup untimed ones from the same initial state;
-`value`, `ms_per_step` and the roofline figures are over those K launches (a longer window is a larger --steps).  At N=1 a
-second leg times the same step on 1 M filters (state 1.17 GB, nothing cache-resident) -> roofline.frac_cache_busting; that leg
-repeats its 24 steps until it lasts >= --min-timed-ms.
+`value`, `ms_per_step` and the roofline figures are over those K launches (a longer window is a larger --steps).
+
+A plain run does only what that line needs: set up, warm up, time the K steps, dump (--dump-outputs), print.  --full adds, at
+N=1 and after the timed steps, what takes runs of its own: a second leg that times the same step on 1 M filters (state 1.17 GB,
+nothing cache-resident) -> roofline.frac_cache_busting, the same 1 M filters in the library's blocked order ->
+roofline.frac_cache_blocked (each leg repeats its 24 steps until it lasts >= --min-timed-ms, resp. half of it), and the CPU
+baselines with the HIP path's parity on their sample -> cpu_baseline.  None of it changes the timed steps or the dumped outputs.
 
 --dump-outputs DIR writes what the timed path left for its caller after the last timed step -- the head state of rank 0's
 filters as getHeadState returns it -- as DIR/<name>.npy (float64); the inputs depend on the arguments only, so two builds
@@ -298,12 +302,16 @@ def main():
                     help="N > 1: weak = --batch-per-gpu filters on EVERY GPU (the default; the line says so); strong = --total-batch "
                          "filters split over the N GPUs -- with the default 262 144 that is BASELINE config 4 (32 768 per GPU at N = 8)")
     ap.add_argument("--total-batch", type=int, default=262144, help="--scaling strong: filters of the whole job")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs the headline does not need (N = 1): the 1 M-filter cache-busting and cache-blocked "
+                         "legs and the CPU baselines with their parity check; a plain run only sets up, warms up, times --steps "
+                         "and prints the line")
     ap.add_argument("--cpu-seconds", type=float, default=6.0,
-                    help="target wall time of the dense CPU baseline sample (the structured one adds <= 3 s: <= 10 s of CPU work in all)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-cache-busting", action="store_true", help="skip the 1 M-filter true-HBM leg (N=1 only)")
+                    help="--full: target wall time of the dense CPU baseline sample (the structured one adds <= 3 s: <= 10 s of CPU work in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-cache-busting", action="store_true", help="--full: skip the 1 M-filter legs (N=1 only)")
     ap.add_argument("--min-timed-ms", type=float, default=6000.0,
-                    help="the 1 M-filter legs repeat their steps until they last at least this long (6 s by default: an "
+                    help="--full: the 1 M-filter legs repeat their steps until they last at least this long (6 s by default: an "
                          "external GPU-busy sampler with a 5 s period must see them); the headline leg times exactly --steps")
     ap.add_argument("--host-streams", action="store_true",
                     help="generate the input streams with the numpy generator on the host (pronto_amd/synth.py) instead of "
@@ -463,7 +471,7 @@ def main():
     hot = est.hot_kernel()
     est.close()
     busting = busting_blocked = None
-    if world == 1 and not args.no_cache_busting and Bper <= (1 << 19):
+    if args.full and world == 1 and not args.no_cache_busting and Bper <= (1 << 19):
         try:
             busting = cache_busting(BatchEstimator, dev, local_rank, n, d_imu, d_lo, d_mask, vec, quat, P0, q4,
                                     args.min_timed_ms)
@@ -493,7 +501,7 @@ def main():
                          "frac": achieved / HBM_PEAK_GBPS, "traffic": None, "traffic_source": None,
                          "kernel_avg_us": launch_s * 1e6, "algorithmic_bytes_per_launch": bps * B,
                          "resident": ("infinity_cache: the %.0f MB state stays in the 256 MB memory-side cache between "
-                                      "launches, so `frac` is NOT an HBM-DRAM rate; see frac_cache_busting" % state_mb)
+                                      "launches, so `frac` is NOT an HBM-DRAM rate; see frac_cache_busting (--full)" % state_mb)
                          if state_mb < 256 else "hbm"},
             "summary": {"sum_loglik": float(summary[0]), "checksum_abs": float(summary[1]),
                         "max_quat_norm_dev": float(summary[2]), "nonfinite": float(summary[3])},
@@ -521,7 +529,7 @@ def main():
             out["fused"] = fused
         if dumped is not None:
             out["dumped_outputs"] = dumped
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(n, dt_us, args.cpu_seconds, BatchEstimator)
         print(json.dumps(out), flush=True)
     if use_dist:

@@ -71,7 +71,7 @@ for K in 64 256; do
   SWEEP_STEPS=$K SWEEP_SIZES=262144,524288 SWEEP_VARIANTS=unblocked,default python3 scripts/batch_sweep.py 21 >> $OUT/batch_sweep.txt 2>&1
 done
 bash scripts/input_footprint.sh > $OUT/n21_input_footprint.txt 2>&1
-python3 bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err
+python3 bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err
 # round 4: forward passes that keep every posterior (per-message into slots vs the write-through replay), the smoother with
 # Eigen's pivoting for comparison, the pair kernels A/B (min of 3)  (independent log segments: scripts/segment_rate.sh, above)
 python3 scripts/checkpoint_rate.py 2>/dev/null | grep "n=" > $OUT/checkpoint_rate.txt
