@@ -374,6 +374,51 @@ int pb_legodo_fk(pb_ctx *ctx, int n_rows, const float *joint_position, const flo
  * leg_odo_init, walking-phase mode (foot_contact_classify.hpp:34-44), transitions the classifier did not know */
 int pb_legodo_get(pb_ctx *ctx, int filter, double odom_to_body[7], int64_t info[4]);
 
+/* ---- yaw lock (YawLockHandler, motion_estimate/src/quick_lock/rbis_yawlock_update.cpp; YawLock::getCorrection,
+ * yawlock.cpp:78-205) ------------------------------------------------------------------------------------------------
+ * While the robot stands, the pose the two standing links had when it came to stand and the leg kinematics now give a
+ * drift-free pelvis orientation (the yaw row of an indexed + orientation measurement), and the body-frame gyro z is a
+ * measurement of the gyro bias z.  The handler is a small state machine PER FILTER -- it reads the filter's own head pose -- kept in
+ * a context-owned array: the two captured world-to-foot poses, the captured left-to-right rotation, utime_disable_until, the
+ * counter, lock_init, and the number of slips detected (the reference publishes YAW_SLIP_DETECTED instead).
+ * The kinematic chain is the one of pb_legodo_set_chain (PB_ERR_STATE without one); joint positions are the RAW message values:
+ * no joint filter, no torque adjustment (rbis_yawlock_update.cpp:188).
+ *
+ * pb_yawlock_init: mode 0 yawbias (idx {17}), 1 yaw (idx {8}), 2 yawbias_yaw (idx {17, 8}); modes 0 and 2 need the 21-state
+ * filter (PB_ERR_ARG on 15 states).  correction_period >= 1.  yaw_slip_disable_period_s: the reference reads it from the key
+ * state_estimator.yawlock.yaw_slip_threshold_degrees (rbis_yawlock_update.cpp:19) -- pass what the caller's configuration gives.
+ * r_yaw_bias_deg / r_yaw_deg: R = (r pi/180)^2.  Every filter's state goes back to the constructor's: counter 0, no lock,
+ * disable_until 0; standing false and gyro z 0 for every filter. */
+int pb_yawlock_init(pb_ctx *ctx, int mode, int correction_period, int yaw_slip_detect, double yaw_slip_threshold_degrees,
+                    double yaw_slip_disable_period_s, double r_yaw_bias_deg, double r_yaw_deg);
+/* What the status handlers (controllerStatusHandler / robotBehaviorHandler) and insHandler keep, until the next call: ONE value
+ * for every filter (PB_HOST_BROADCAST) or [B] values (PB_HOST / PB_DEVICE; copied before the call returns). */
+int pb_yawlock_set_standing(pb_ctx *ctx, const uint8_t *standing, int mem);
+int pb_yawlock_set_gyro(pb_ctx *ctx, const double *body_gyro_z, int mem);
+/* YawLockHandler::processMessage for every filter, FORM only (diagnostics; a caller that applies the update later): runs the
+ * state machine and writes (DEVICE arrays, each may be NULL)
+ *   z_out [2][B]     row 0 = the bias measurement (gyro z while standing, else the head's own gyro bias z), row 1 = 0
+ *   quat_out [4][B]  the orientation measurement (w x y z; identity where there is none)
+ *   mask_out [2][B]  row 0: apply the mode's row set with the orientation (pb_update_indexed_orient with idx {8} / {17, 8},
+ *                    R = {r_yaw^2} / {r_yaw_bias^2, r_yaw^2}); row 1: apply the bias row alone (pb_update_indexed, idx {17}).
+ *                    Neither = the handler returned NULL for this filter.
+ * joint_position: [n_rows][B] floats (PB_HOST / PB_DEVICE) or ONE robot's [n_rows] values (PB_HOST_BROADCAST).
+ * utimes / valid: DEVICE arrays [B] or NULL (batches of independent log segments): the message time per filter instead of
+ * `utime`; valid == 0 = no message for this filter, which keeps its state, its counter included.  The filter state is not touched. */
+int pb_yawlock_update_joints(pb_ctx *ctx, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                             const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out);
+/* The same, formed AND APPLIED in one kernel (k_step_yawlock): a filter without an update leaves after the small read without
+ * touching its covariance; one with an update makes one round trip of its state.  Equal to pb_yawlock_update_joints followed by
+ * pb_update_indexed_orient / pb_update_indexed with the two masks, to rounding.  Honours pb_set_output_slot; writes no predicted
+ * posterior (a pending pb_set_pred_slot is refused and forgotten).  The optional outputs are the measurement that was applied,
+ * for a caller that may have to re-apply it later (history replay) -- the state machine itself must not run twice. */
+int pb_step_yawlock_joints(pb_ctx *ctx, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                           const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out);
+/* one filter's yaw-lock state, for diagnostics and tests: poses = world_to_l_foot_original, world_to_r_foot_original (t3, q4
+ * each); info = counter, lock_init, utime_disable_until, last outcome (low 8 bits: 0 no message, 1 not a correction tick, 2 not
+ * standing, 3 held off after a slip, 4 captured, 5 slip detected, 6 correction, 7 mode yawbias; the rest: slips so far << 8) */
+int pb_yawlock_get(pb_ctx *ctx, int filter, double poses[14], int64_t info[4]);
+
 /* ---- IMU front end of the Atlas path (InsHandler::doFilter, sensor_handlers.cpp:29-42,154-162) ---------------- */
 
 /* Three cascaded 2nd-order IIR notches (iir_notch.cpp:3-61) at notch_freq * 2^i, i = 0..2, per accelerometer axis and

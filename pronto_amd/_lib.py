@@ -120,6 +120,14 @@ _SIGS = {
     "pb_joint_filter_init": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),
     "pb_joint_filter": (C.c_int, [C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pb_legodo_get": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_int64)]),
+    "pb_yawlock_init": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "pb_yawlock_set_standing": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "pb_yawlock_set_gyro": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
+    "pb_yawlock_update_joints": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                           C.c_void_p]),
+    "pb_step_yawlock_joints": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.c_void_p]),
+    "pb_yawlock_get": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_int64)]),
     "pb_imu_notch_init": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "pb_imu_notch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_history_reserve": (C.c_int, [C.c_void_p, C.c_int]),

@@ -370,6 +370,65 @@ class BatchEstimator:
         self._chk(self._L.pb_legodo_get(self._h, b, pose, info))
         return np.array(pose), [int(v) for v in info]
 
+    # --- yaw lock (YawLockHandler) ---
+    YAWLOCK_MODES = {"yawbias": 0, "yaw": 1, "yawbias_yaw": 2}
+
+    def yawlock_init(self, mode, correction_period, yaw_slip_detect, yaw_slip_threshold_degrees, yaw_slip_disable_period_s, r_yaw_bias_deg=0.0,
+                     r_yaw_deg=0.0):
+        """mode: "yawbias" | "yaw" | "yawbias_yaw" (or 0 / 1 / 2); resets every filter's yaw-lock state."""
+        self._chk(self._L.pb_yawlock_init(self._h, int(self.YAWLOCK_MODES.get(mode, mode)), int(correction_period), int(bool(yaw_slip_detect)),
+                                          float(yaw_slip_threshold_degrees), float(yaw_slip_disable_period_s), float(r_yaw_bias_deg),
+                                          float(r_yaw_deg)))
+
+    def yawlock_set_standing(self, standing):
+        """one bool for every filter, or a [B] uint8 array / tensor"""
+        if np.isscalar(standing) or isinstance(standing, bool):
+            v = (C.c_uint8 * 1)(1 if standing else 0)
+            self._chk(self._L.pb_yawlock_set_standing(self._h, v, PB_HOST_BROADCAST))
+        else:
+            p, m = _ptr(standing, np.uint8, shape=(self.B,))
+            self._chk(self._L.pb_yawlock_set_standing(self._h, p, m))
+
+    def yawlock_set_gyro(self, body_gyro_z):
+        """the body-frame gyro z YawLockHandler::insHandler keeps: one value for every filter, or [B]"""
+        if np.isscalar(body_gyro_z):
+            v = (C.c_double * 1)(float(body_gyro_z))
+            self._chk(self._L.pb_yawlock_set_gyro(self._h, v, PB_HOST_BROADCAST))
+        else:
+            p, m = _ptr(body_gyro_z, shape=(self.B,))
+            self._chk(self._L.pb_yawlock_set_gyro(self._h, p, m))
+
+    def _yawlock_call(self, fn, utime, joint_position, utimes, valid, z_out, quat_out, mask_out):
+        rows = joint_position.shape[0]
+        pj, mj = _ptr_block(joint_position, rows, self.B, dtype=np.float32)
+        pu = None if utimes is None else C.c_void_p(utimes.data_ptr())
+        pv = None if valid is None else C.c_void_p(valid.data_ptr())
+        for t, shape in ((utimes, (self.B,)), (valid, (self.B,))):
+            if t is not None and (tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous()):
+                raise ValueError("utimes / valid must be contiguous device tensors of shape [B]")
+        pz, m1 = _ptr(z_out, shape=(2, self.B))
+        pq, m2 = _ptr(quat_out, shape=(4, self.B))
+        pm, m3 = _ptr(mask_out, np.uint8, shape=(2, self.B))
+        if any(m is not None and m != PB_DEVICE for m in (m1, m2, m3)):
+            raise ValueError("yaw-lock outputs must be device tensors")
+        self._chk(fn(self._h, int(utime), pu, pv, rows, pj, mj, pz, pq, pm))
+
+    def yawlock_update_joints(self, utime, joint_position, utimes=None, valid=None, z_out=None, quat_out=None, mask_out=None):
+        """YawLockHandler::processMessage, form only: z_out [2,B], quat_out [4,B], mask_out [2,B] device tensors."""
+        self._yawlock_call(self._L.pb_yawlock_update_joints, utime, joint_position, utimes, valid, z_out, quat_out, mask_out)
+
+    def step_yawlock_joints(self, utime, joint_position, utimes=None, valid=None, z_out=None, quat_out=None, mask_out=None):
+        """the same, formed and applied in one kernel: pb_step_yawlock_joints"""
+        self._yawlock_call(self._L.pb_step_yawlock_joints, utime, joint_position, utimes, valid, z_out, quat_out, mask_out)
+
+    def yawlock_get(self, b):
+        """(poses [14], dict(counter, lock_init, disable_until, outcome, slips)) of filter b"""
+        poses = (C.c_double * 14)()
+        info = (C.c_int64 * 4)()
+        self._chk(self._L.pb_yawlock_get(self._h, int(b), poses, info))
+        return np.array(poses), dict(counter=int(info[0]), lock_init=int(info[1]), disable_until=int(info[2]), outcome=int(info[3]) & 255,
+                                     slips=int(info[3]) >> 8)
+
     # --- IMU front end ---
     def imu_notch_init(self, notch_freq, fs=1000.0):
         self._chk(self._L.pb_imu_notch_init(self._h, notch_freq, fs))

@@ -465,6 +465,82 @@ public:
   bool appliesToNoFilter(pb_ctx *ctx, int B) override { return first->appliesToNoFilter(ctx, B) && second->appliesToNoFilter(ctx, B); }
 };
 
+// the joint positions of one message as an update takes them over
+struct msgs_joint_ref {
+  const float *p;
+  int n_rows, mem;
+};
+
+// What YawLockHandler::processMessage returns (rbis_yawlock_update.cpp:193-228): an RBISIndexedMeasurement /
+// RBISIndexedPlusOrientationMeasurement whose content depends on each filter's own head pose and yaw-lock state, so it is FORMED on
+// the device, when the update is first applied (MavStateEstimator::addUpdate: the head is then the state at its place in the
+// history), by the kernel that also applies it -- pb_step_yawlock_joints.  The update owns the joint positions of its message
+// and, from then on, the measurement that was applied: z [2][B], quaternion [4][B], masks [2][B] in one device block.  A
+// delayed-measurement replay re-applies THAT (pb_update_indexed_orient / pb_update_indexed with the two masks); the state machine
+// never runs twice for one message.
+class RBISYawLockUpdate : public RBISUpdateInterface {
+public:
+  int mode;                            // 0 yawbias, 1 yaw, 2 yawbias_yaw
+  std::vector<float> joint_position;   // one robot's raw joint positions (PB_HOST_BROADCAST), or empty: joint_dev
+  const float *joint_dev = nullptr;    // [rows][B] device block of the caller (valid until the update has been applied)
+  int n_rows, joints_mem;
+  uint8_t standing;                    // what the status handler last decided
+  double gyro_z;                       // body-frame gyro z of the last IMU message (insHandler)
+  double R[2];                         // the diagonal of the mode's row set
+  double r_bias;
+  std::shared_ptr<DeviceBlock> kept;   // z | quat | masks
+  bool formed = false;
+  RBISYawLockUpdate(int mode_, const msgs_joint_ref &j, uint8_t standing_, double gyro_z_, double r_bias_, double r_yaw_,
+                    std::shared_ptr<DeviceBlock> block, int64_t utime)
+      : RBISUpdateInterface(yawlock, utime), mode(mode_), n_rows(j.n_rows), joints_mem(j.mem), standing(standing_), gyro_z(gyro_z_),
+        r_bias(r_bias_), kept(std::move(block))
+  {
+    if (j.mem == PB_HOST_BROADCAST) joint_position.assign(j.p, j.p + j.n_rows);
+    else joint_dev = j.p;
+    R[0] = mode == 1 ? r_yaw_ : r_bias_;
+    R[1] = r_yaw_;
+  }
+  double *z(int B) const { (void) B; return (double *) kept->p; }
+  double *quat(int B) const { return (double *) kept->p + 2 * (size_t) B; }
+  uint8_t *masks(int B) const { return (uint8_t *) ((double *) kept->p + 6 * (size_t) B); }
+  int updateFilter(pb_ctx *ctx) override
+  {
+    const int B = pb_batch(ctx);
+    if (!formed) {
+      formed = true;
+      int rc = pb_yawlock_set_standing(ctx, &standing, PB_HOST_BROADCAST);
+      if (rc == PB_OK) rc = pb_yawlock_set_gyro(ctx, &gyro_z, PB_HOST_BROADCAST);
+      if (rc != PB_OK) return rc;
+      return pb_step_yawlock_joints(ctx, utime, nullptr, nullptr, n_rows, joint_position.empty() ? joint_dev : joint_position.data(), joints_mem,
+                                    z(B), quat(B), masks(B));
+    }
+    // a replay: the kept measurement, the row set with the orientation and / or the bias row alone (complementary masks; if the
+    // first half wrote into a checkpoint slot, the second works in place on it, as RBISEitherUpdate)
+    int rc = PB_OK;
+    if (mode != 0) {
+      const int idx[2] = { mode == 1 ? 8 : 17, 8 };
+      rc = pb_update_indexed_orient(ctx, mode == 1 ? 1 : 2, idx, z(B), R, PB_R_DIAG_BROADCAST, quat(B), masks(B), PB_DEVICE);
+      if (rc != PB_OK || mode == 1) return rc;
+      const int slot = pb_head_slot(ctx);
+      if (slot >= 0) pb_set_output_slot(ctx, slot);
+    }
+    const int idx1[1] = { 17 };
+    return pb_update_indexed(ctx, 1, idx1, z(B), &r_bias, PB_R_DIAG_BROADCAST, masks(B) + B, PB_DEVICE);
+  }
+  // the batch-wide idle message (no filter gets an update): known once the measurement has been formed
+  bool appliesToNoFilter(pb_ctx *ctx, int B) override
+  {
+    if (!formed) return false;
+    if (empty_known_) return empty_;
+    int n0 = 1, n1 = 1;
+    if (pb_mask_count(ctx, masks(B), &n0) != PB_OK || pb_mask_count(ctx, masks(B) + B, &n1) != PB_OK) return false;
+    empty_known_ = true;
+    return empty_ = (n0 + n1 == 0);
+  }
+private:
+  bool empty_known_ = false, empty_ = false;
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // updateHistory + MavStateEstimator (update_history.hpp:12-36, mav_state_est.hpp / .cpp:12-96)
 //
@@ -1258,6 +1334,19 @@ struct six_axis_force_torque_array_t {   // bot_core::six_axis_force_torque_arra
 struct controller_foot_contact_t {       // pronto::controller_foot_contact_t
   int64_t utime;
   int32_t num_left_foot_contacts, num_right_foot_contacts;
+};
+struct controller_status_t {   // pronto::controller_status_t (pronto_controller_status_t.lcm)
+  enum { UNKNOWN = 0, STANDING = 1, WALKING = 2, HARNESSED = 3, QUASISTATIC = 4, BRACING = 5, CRAWLING = 6, DUMMY = 7, MANIPULATING = 8 };
+  int64_t utime = 0;
+  int8_t state = UNKNOWN;
+  int64_t controller_utime = 0;
+  float V = 0, Vdot = 0;
+};
+struct behavior_t {            // pronto::behavior_t (pronto_behavior_t.lcm)
+  enum { BEHAVIOR_NONE = 0, BEHAVIOR_FREEZE = 1, BEHAVIOR_STAND_PREP = 2, BEHAVIOR_STAND = 3, BEHAVIOR_WALK = 4, BEHAVIOR_STEP = 5,
+         BEHAVIOR_MANIPULATE = 6, BEHAVIOR_USER = 7, BEHAVIOR_CALIBRATE = 8, BEHAVIOR_SOFT_STOP = 9 };
+  int64_t utime = 0;
+  int32_t behavior = BEHAVIOR_NONE;
 };
 struct update_t {            // pronto::update_t (fovis)
   int64_t timestamp, prev_timestamp;
@@ -2492,6 +2581,114 @@ public:
 // The reference's update objects own their measurement (Eigen copies in their constructors); so do ours for host data,
 // which the history may re-apply long after the message buffer is gone.  Device blocks are referenced, not copied: the
 // caller keeps them alive for utime_history_span.  cov_diag must outlive the update (handlers are app-lifetime singletons).
+// ---------------------------------------------------------------------------------------------------------------
+// YawLockHandler (motion_estimate/src/quick_lock/rbis_yawlock_update.cpp): the reference's constructor (lcm_recv, lcm_pub, param,
+// model, frames) without the LCM objects; `ins_to_body` is what it takes from BotFrames (:45-47).  The caller routes the status
+// channel named by behavior_channel to controllerStatusHandler / robotBehaviorHandler and the IMU channel to insHandler, and adds
+// processMessage as sensor "yawlock" (FrontEnd::addSensor) behind the LegOdoHandler of the same joint-state channel
+// (fusion.cpp:233-241 registers legodo first): the kinematic chain on the device is the one that handler sets.
+// The state machine itself (YawLock::getCorrection) lives per filter on the device, rbis_yawlock.hpp.
+// ---------------------------------------------------------------------------------------------------------------
+class YawLockHandler {
+public:
+  enum YawLockMode { MODE_YAWBIAS = 0, MODE_YAW = 1, MODE_YAWBIAS_YAW = 2 };
+  YawLockMode mode;
+  int correction_period;
+  bool yaw_slip_detect;
+  double yaw_slip_threshold_degrees, yaw_slip_disable_period, r_yaw_bias = 0.0, r_yaw = 0.0;
+  std::string behavior_channel, left_standing_link, right_standing_link;
+  BotTrans ins_to_body;
+  double body_gyro[3] = { 0, 0, 0 };
+  bool is_robot_standing = false;        // yaw_lock_->setIsRobotStanding (yawlock.cpp:60: false at the start)
+  int64_t last_ihmc_walking_utime = 0;   // rbis_yawlock_update.cpp:107
+  int64_t idle_messages = 0;             // messages whose update reached no filter (the reference's NULL return), counted lazily
+
+  YawLockHandler(BotParam *param, const ModelClient *model, const BotTrans *ins_to_body_ = nullptr) : model_(model)
+  {
+    correction_period = (int) bot_param_get_int_or_fail(param, "state_estimator.yawlock.correction_period");
+    yaw_slip_detect = bot_param_get_boolean_or_fail(param, "state_estimator.yawlock.yaw_slip_detect");
+    yaw_slip_threshold_degrees = bot_param_get_double_or_fail(param, "state_estimator.yawlock.yaw_slip_threshold_degrees");
+    // NB the reference reads yaw_slip_disable_period from the key yaw_slip_threshold_degrees (rbis_yawlock_update.cpp:19):
+    // mirrored as it is, a threshold of 1.5 degrees is also a hold-off of 1.5 seconds
+    yaw_slip_disable_period = bot_param_get_double_or_fail(param, "state_estimator.yawlock.yaw_slip_threshold_degrees");
+    behavior_channel = bot_param_get_str_or_fail(param, "state_estimator.yawlock.behavior_channel");
+    left_standing_link = bot_param_get_str_or_fail(param, "state_estimator.legodo.left_standing_link");
+    right_standing_link = bot_param_get_str_or_fail(param, "state_estimator.legodo.right_standing_link");
+    if (behavior_channel != "CONTROLLER_STATUS" && behavior_channel != "ROBOT_BEHAVIOR") {  // :30-41
+      fprintf(stdout, "behavior_channel not recognised: CONTROLLER_STATUS or ROBOT_BEHAVIOR\n");
+      exit(-1);
+    }
+    if (ins_to_body_) ins_to_body = *ins_to_body_;
+    const std::string mode_str = bot_param_get_str_or_fail(param, "state_estimator.yawlock.mode");
+    if (mode_str == "yawbias") mode = MODE_YAWBIAS;
+    else if (mode_str == "yaw") mode = MODE_YAW;
+    else if (mode_str == "yawbias_yaw") mode = MODE_YAWBIAS_YAW;
+    else {  // :66-69
+      mode = MODE_YAW;
+      fprintf(stdout, "Unrecognized scan matcher mode. Will reject yaw drift by default.\n");
+    }
+    if (mode != MODE_YAW) r_yaw_bias = bot_param_get_double_or_fail(param, "state_estimator.yawlock.r_yaw_bias");  // :79, :93 deg per sec
+    if (mode != MODE_YAWBIAS) r_yaw = bot_param_get_double_or_fail(param, "state_estimator.yawlock.r_yaw");       // :87, :94
+  }
+
+  // rbis_yawlock_update.cpp:112-116: the gyro in the body frame
+  void insHandler(const msgs::ins_t *msg)
+  {
+    // (one robot's message, PB_HOST_BROADCAST, or filter 0's sample of a per-filter HOST block: the handler keeps one value)
+    const double g[3] = { msg->gyro.p[0], msg->gyro.mem == PB_HOST_BROADCAST ? msg->gyro.p[1] : msg->gyro.p[(size_t) gyro_stride_],
+                          msg->gyro.mem == PB_HOST_BROADCAST ? msg->gyro.p[2] : msg->gyro.p[2 * (size_t) gyro_stride_] };
+    bot_quat_rotate_to(ins_to_body.rot_quat, g, body_gyro);
+  }
+  // MIT / Drake status (:125-137)
+  void controllerStatusHandler(const msgs::controller_status_t *msg)
+  {
+    is_robot_standing = msg->state == msgs::controller_status_t::STANDING || msg->state == msgs::controller_status_t::MANIPULATING;
+  }
+  // IHMC status (:140-158)
+  void robotBehaviorHandler(const msgs::behavior_t *msg)
+  {
+    bool standing = msg->behavior == msgs::behavior_t::BEHAVIOR_STAND || msg->behavior == msgs::behavior_t::BEHAVIOR_MANIPULATE;
+    // "IHMC's behavior message is faulty: it reports the robot standing when it is finishing the last few seconds of a walking
+    // plan" (rbis_yawlock_update.cpp:146-154): less than 3 s after the last BEHAVIOR_WALK counts as not standing
+    if (msg->behavior == msgs::behavior_t::BEHAVIOR_WALK) last_ihmc_walking_utime = msg->utime;
+    if (msg->utime - last_ihmc_walking_utime < 3E6) standing = false;
+    is_robot_standing = standing;
+  }
+
+  // rbis_yawlock_update.cpp:168-232.  Never NULL for the batch: which filters get which row set is decided per filter on the
+  // device when the update is applied; a message that reaches no filter is an update with two empty masks
+  // (RBISUpdateInterface::appliesToNoFilter), as LegOdoHandler's per-filter NULL returns are.
+  RBISUpdateInterface *processMessage(const msgs::joint_state_t *msg, MavStateEstimator *est)
+  {
+    if (!ready_) {
+      if (pb_yawlock_init(est->ctx, (int) mode, correction_period, yaw_slip_detect, yaw_slip_threshold_degrees, yaw_slip_disable_period,
+                          r_yaw_bias, r_yaw) != PB_OK) {
+        fprintf(stderr, "YawLockHandler: %s\n", pb_last_error(est->ctx));
+        exit(1);
+      }
+      pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, (sizeof(double) * 6 + 2) * (size_t) est->B);
+      gyro_stride_ = est->B;
+      ready_ = true;
+    }
+    if (msg->mem == PB_HOST) {
+      fprintf(stderr, "YawLockHandler: joint positions must be PB_HOST_BROADCAST (one robot) or PB_DEVICE blocks\n");
+      return nullptr;
+    }
+    bool fresh = false;
+    void *blk = pool_->get(fresh);
+    if (blk == nullptr) return nullptr;
+    const msgs_joint_ref j{ msg->joint_position, (int) msg->joint_name.size(), msg->mem };
+    return new RBISYawLockUpdate((int) mode, j, is_robot_standing ? 1 : 0, body_gyro[2], bot_sq(bot_to_radians(r_yaw_bias)),
+                                 bot_sq(bot_to_radians(r_yaw)), std::make_shared<DeviceBlock>(pool_, blk), msg->utime);
+  }
+
+private:
+  const ModelClient *model_;
+  std::shared_ptr<DevicePool> pool_;
+  int gyro_stride_ = 1;
+  bool ready_ = false;
+};
+
 inline RBISIndexedMeasurement *makeIndexedMeasurement(const std::vector<int> &idx, BatchArray z, int B,
                                                       const std::vector<double> &cov_diag, const uint8_t *mask,
                                                       RBISUpdateInterface::sensor_enum sensor, int64_t utime)
@@ -3273,6 +3470,33 @@ public:
       msg.translation = BatchArray(w.translation, PB_HOST_BROADCAST);
       msg.rotation = BatchArray(w.rotation, PB_HOST_BROADCAST);
       cb(&msg);
+    };
+  }
+  // the two status channels of YawLockHandler (fixed-size pronto types, pronto_wire.hpp)
+  void subscribeControllerStatus(const std::string &channel, std::function<void(const msgs::controller_status_t *)> cb)
+  {
+    subs_[channel] = [this, cb](const pronto_wire::LogEvent &ev) {
+      pronto_wire::controller_status_t w;
+      if (w.decode(ev.data.data(), ev.data.size()) < 0) {
+        n_bad_++;
+        return;
+      }
+      msgs::controller_status_t m;
+      m.utime = w.utime; m.state = w.state; m.controller_utime = w.controller_utime; m.V = w.V; m.Vdot = w.Vdot;
+      cb(&m);
+    };
+  }
+  void subscribeBehavior(const std::string &channel, std::function<void(const msgs::behavior_t *)> cb)
+  {
+    subs_[channel] = [this, cb](const pronto_wire::LogEvent &ev) {
+      pronto_wire::behavior_t w;
+      if (w.decode(ev.data.data(), ev.data.size()) < 0) {
+        n_bad_++;
+        return;
+      }
+      msgs::behavior_t m;
+      m.utime = w.utime; m.behavior = w.behavior;
+      cb(&m);
     };
   }
   // returns the number of events dispatched, or -1 if the file cannot be opened

@@ -15,6 +15,7 @@
 #include "rbis_legodo.hpp"
 #include "rbis_legstep.hpp"
 #include "rbis_jointfilt.hpp"
+#include "rbis_yawlock.hpp"
 
 using namespace pb;
 
@@ -58,6 +59,15 @@ struct pb_ctx {
   std::vector<float> jf_ring_h;   // [JF_TAPS][nf]   (one robot)
   std::vector<double> jf_kst_h;   // [JF_KSTATE][nf]
   double *leg_lo = nullptr;       // measurement block + mask between the two kernels of pb_step_legodo_joints' fallback path
+  // yaw lock (pb_yawlock_init, rbis_yawlock.hpp): per-filter state [NYD][stride] doubles + [NYI][stride] 64-bit words
+  YawPar yaw_par;
+  double *yawd = nullptr;
+  int64_t *yawi = nullptr;
+  uint8_t *yaw_standing = nullptr;  // what the status / IMU handlers keep (pb_yawlock_set_standing / _set_gyro): [stride] device
+  double *yaw_gyro = nullptr;       // arrays, used when the matching *_dev is set, or ONE value for every filter
+  bool yaw_standing_dev = false, yaw_gyro_dev = false;
+  int yaw_standing_all = 0;
+  double yaw_gyro_all = 0.0;
   double *notch = nullptr;  // IMU notch cascade state [36][stride] (pb_imu_notch_init)
   NotchCoef notch_coef;
   bool notch_ready = false;
@@ -190,3 +200,9 @@ int pbk_smooth_step(pb_ctx *c, const double *next_pred, const double *next_sm, c
 int pbk_smooth_wide(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);   // 15 states (pb_smooth_wide.hip)
 // pb_select.hip: dst <- src for the filters whose mask_dev entry (device, [B]; non-zero counts as 1) equals `when`, every other column untouched
 int pbk_slot_select(pb_ctx *c, double *dst, const double *src, const uint8_t *mask_dev, int when);
+// pb_yawlock.hip: the yaw-lock handler (rbis_yawlock.hpp).  form: state machine + measurement block + masks; step: the same and the
+// update applied in the one kernel (honours pb_set_output_slot).  z_out [2][B], quat_out [4][B], mask_out [2][B] device or NULL (step)
+int pbk_yawlock_reset(pb_ctx *c);
+int pbk_yawlock_get(pb_ctx *c, int filter, double *poses_dev, int64_t *info_dev);
+int pbk_yawlock_form(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out);
+int pbk_step_yawlock(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out);

@@ -161,6 +161,10 @@ extern "C" int pb_destroy(pb_ctx *c)
   if (c->leg_valid) (void) hipFree(c->leg_valid);
   if (c->leg_nc) (void) hipFree(c->leg_nc);
   if (c->leg_lo) (void) hipFree(c->leg_lo);
+  if (c->yawd) (void) hipFree(c->yawd);
+  if (c->yawi) (void) hipFree(c->yawi);
+  if (c->yaw_standing) (void) hipFree(c->yaw_standing);
+  if (c->yaw_gyro) (void) hipFree(c->yaw_gyro);
   if (c->jf_ring) (void) hipFree(c->jf_ring);
   if (c->jf_kst) (void) hipFree(c->jf_kst);
   if (c->d_small) (void) hipFree(c->d_small);
@@ -1681,6 +1685,119 @@ extern "C" int pb_legodo_get(pb_ctx *c, int filter, double odom_to_body[7], int6
   k_legodo_get<<<1, 1, 0, c->stream>>>(c->legd, c->legi, c->stride, filter, dp, di);
   LAUNCHCHK(c);
   HIPCHK(c, hipMemcpyAsync(odom_to_body, dp, sizeof(double) * 7, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, di, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PB_OK;
+}
+
+// ---- yaw lock (rbis_yawlock.hpp, pb_yawlock.hip) ----------------------------------------------------------------------------
+extern "C" int pb_yawlock_init(pb_ctx *c, int mode, int correction_period, int yaw_slip_detect, double yaw_slip_threshold_degrees,
+                               double yaw_slip_disable_period_s, double r_yaw_bias_deg, double r_yaw_deg)
+{
+  if (!c) return PB_ERR_ARG;
+  // (the argument checks come before anything that needs the device)
+  if (mode < YL_YAWBIAS || mode > YL_YAWBIAS_YAW) return fail(c, PB_ERR_ARG, "pb_yawlock_init: mode must be 0 (yawbias), 1 (yaw) or 2 (yawbias_yaw)");
+  if (mode != YL_YAW && c->ns != 21) return fail(c, PB_ERR_ARG, "pb_yawlock_init: mode %d measures the gyro bias (state 17), this context has %d states", mode, c->ns);
+  if (correction_period < 1) return fail(c, PB_ERR_ARG, "pb_yawlock_init: correction_period must be >= 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (!c->yawd) HIPCHK(c, hipMalloc((void **) &c->yawd, sizeof(double) * NYD * (size_t) c->stride));
+  if (!c->yawi) HIPCHK(c, hipMalloc((void **) &c->yawi, sizeof(int64_t) * NYI * (size_t) c->stride));
+  YawPar &p = c->yaw_par;
+  p.mode = mode;
+  p.period = correction_period;
+  p.slip_detect = yaw_slip_detect != 0;
+  p.slip_threshold_deg = yaw_slip_threshold_degrees;
+  p.slip_disable_s = yaw_slip_disable_period_s;
+  const double rb = r_yaw_bias_deg * M_PI / 180.0, ry = r_yaw_deg * M_PI / 180.0;  // bot_to_radians, bot_sq (rbis_yawlock_update.cpp:80,88)
+  p.r_bias = rb * rb;
+  p.r_yaw = ry * ry;
+  c->yaw_standing_dev = c->yaw_gyro_dev = false;
+  c->yaw_standing_all = 0;
+  c->yaw_gyro_all = 0.0;
+  return pbk_yawlock_reset(c);
+}
+
+extern "C" int pb_yawlock_set_standing(pb_ctx *c, const uint8_t *standing, int mem)
+{
+  ENTER(c);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_standing before pb_yawlock_init");
+  if (!standing) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: NULL input");
+  if (mem == PB_HOST_BROADCAST) {
+    c->yaw_standing_all = standing[0] != 0;
+    c->yaw_standing_dev = false;
+    return PB_OK;
+  }
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: bad mem");
+  if (!c->yaw_standing) HIPCHK(c, hipMalloc((void **) &c->yaw_standing, (size_t) c->stride));
+  HIPCHK(c, hipMemcpyAsync(c->yaw_standing, standing, (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+  if (mem == PB_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+  c->yaw_standing_dev = true;
+  return PB_OK;
+}
+
+extern "C" int pb_yawlock_set_gyro(pb_ctx *c, const double *body_gyro_z, int mem)
+{
+  ENTER(c);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_gyro before pb_yawlock_init");
+  if (!body_gyro_z) return fail(c, PB_ERR_ARG, "pb_yawlock_set_gyro: NULL input");
+  if (mem == PB_HOST_BROADCAST) {
+    c->yaw_gyro_all = body_gyro_z[0];
+    c->yaw_gyro_dev = false;
+    return PB_OK;
+  }
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_yawlock_set_gyro: bad mem");
+  if (!c->yaw_gyro) HIPCHK(c, hipMalloc((void **) &c->yaw_gyro, sizeof(double) * (size_t) c->stride));
+  HIPCHK(c, hipMemcpyAsync(c->yaw_gyro, body_gyro_z, sizeof(double) * (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                           c->stream));
+  if (mem == PB_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->yaw_gyro_dev = true;
+  return PB_OK;
+}
+
+static int yawlock_impl(pb_ctx *c, const char *who, bool apply, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                        const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  ENTER(c);
+  NEED_STATE(c);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "%s before pb_yawlock_init", who);
+  LegIn lin;
+  int rc = leg_in_joints(c, who, n_rows, joint_position, nullptr, nullptr, mem, lin);
+  if (rc) return rc;
+  lin.utimes = utimes;
+  lin.valid = valid;
+  YawIn yin;
+  yin.standing = c->yaw_standing_dev ? c->yaw_standing : nullptr;
+  yin.gyro_z = c->yaw_gyro_dev ? c->yaw_gyro : nullptr;
+  yin.standing_all = c->yaw_standing_all;
+  yin.gyro_z_all = c->yaw_gyro_all;
+  return apply ? pbk_step_yawlock(c, yin, lin, utime, z_out, quat_out, mask_out) : pbk_yawlock_form(c, yin, lin, utime, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_yawlock_update_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                                        const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  return yawlock_impl(c, "pb_yawlock_update_joints", false, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_step_yawlock_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                                      const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  if (int rc = refuse_pred(c, "pb_step_yawlock_joints")) return rc;
+  return yawlock_impl(c, "pb_step_yawlock_joints", true, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_yawlock_get(pb_ctx *c, int filter, double poses[14], int64_t info[4])
+{
+  ENTER(c);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_get before pb_yawlock_init");
+  if (filter < 0 || filter >= c->B || !poses || !info) return fail(c, PB_ERR_ARG, "pb_yawlock_get: bad argument");
+  int rc = stage_reserve(c, 256);
+  if (rc) return rc;
+  double *dp = (double *) c->stage;
+  int64_t *di = (int64_t *) (dp + 16);
+  rc = pbk_yawlock_get(c, filter, dp, di);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(poses, dp, sizeof(double) * 14, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(info, di, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PB_OK;

@@ -61,6 +61,7 @@ public:
   int32_t i32() { return (int32_t) u32(); }
   uint64_t u64() { if (!need(8)) return 0; uint64_t v = 0; for (int i = 0; i < 8; i++) v = (v << 8) | p[pos++]; return v; }
   int64_t i64() { return (int64_t) u64(); }
+  float f32() { uint32_t u = u32(); float v; memcpy(&v, &u, 4); return v; }
   double f64() { uint64_t u = u64(); double v; memcpy(&v, &u, 8); return v; }
   void f64s(double *v, size_t k) { for (size_t i = 0; i < k; i++) v[i] = f64(); }
 };
@@ -271,6 +272,75 @@ struct update_t {
     r.f64s(rotation, 4);
     for (int i = 0; i < 6; i++) r.f64s(covariance[i], 6);
     estimate_status = r.i8();
+    return r.ok ? (int) r.pos : WIRE_ERR_SHORT;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
+// pronto::controller_status_t / pronto::behavior_t (pronto_controller_status_t.lcm, pronto_behavior_t.lcm): the two status
+// channels YawLockHandler listens to (rbis_yawlock_update.cpp:30-41).  Both are fixed-size.
+// ---------------------------------------------------------------------------------------------------------------
+struct controller_status_t {
+  enum { UNKNOWN = 0, STANDING = 1, WALKING = 2, HARNESSED = 3, QUASISTATIC = 4, BRACING = 5, CRAWLING = 6, DUMMY = 7, MANIPULATING = 8 };
+  int64_t utime = 0;
+  int8_t state = UNKNOWN;
+  int64_t controller_utime = 0;
+  float V = 0, Vdot = 0;
+  static const std::vector<Member> &members()
+  {
+    static const std::vector<Member> m = { { "utime", "int64_t", {} }, { "state", "int8_t", {} }, { "controller_utime", "int64_t", {} },
+                                           { "V", "float", {} }, { "Vdot", "float", {} } };
+    return m;
+  }
+  static uint64_t fingerprint() { static const uint64_t f = lcm_fingerprint(members()); return f; }
+  void encode(std::vector<uint8_t> &out) const
+  {
+    Writer w;
+    w.u64(fingerprint());
+    w.i64(utime);
+    w.i8(state);
+    w.i64(controller_utime);
+    w.f32(V);
+    w.f32(Vdot);
+    out.swap(w.buf);
+  }
+  int decode(const void *data, size_t len)
+  {
+    Reader r(data, len);
+    if (r.u64() != fingerprint()) return r.ok ? WIRE_ERR_FINGERPRINT : WIRE_ERR_SHORT;
+    utime = r.i64();
+    state = r.i8();
+    controller_utime = r.i64();
+    V = r.f32();
+    Vdot = r.f32();
+    return r.ok ? (int) r.pos : WIRE_ERR_SHORT;
+  }
+};
+struct behavior_t {
+  enum { BEHAVIOR_NONE = 0, BEHAVIOR_FREEZE = 1, BEHAVIOR_STAND_PREP = 2, BEHAVIOR_STAND = 3, BEHAVIOR_WALK = 4, BEHAVIOR_STEP = 5,
+         BEHAVIOR_MANIPULATE = 6, BEHAVIOR_USER = 7, BEHAVIOR_CALIBRATE = 8, BEHAVIOR_SOFT_STOP = 9 };
+  int64_t utime = 0;
+  int32_t behavior = BEHAVIOR_NONE;
+  static const std::vector<Member> &members()
+  {
+    static const std::vector<Member> m = { { "utime", "int64_t", {} }, { "behavior", "int32_t", {} } };
+    return m;
+  }
+  static uint64_t fingerprint() { static const uint64_t f = lcm_fingerprint(members()); return f; }
+  void encode(std::vector<uint8_t> &out) const
+  {
+    Writer w;
+    w.u64(fingerprint());
+    w.i64(utime);
+    w.i32(behavior);
+    out.swap(w.buf);
+  }
+  int decode(const void *data, size_t len)
+  {
+    Reader r(data, len);
+    if (r.u64() != fingerprint()) return r.ok ? WIRE_ERR_FINGERPRINT : WIRE_ERR_SHORT;
+    utime = r.i64();
+    behavior = r.i32();
     return r.ok ? (int) r.pos : WIRE_ERR_SHORT;
   }
 };
