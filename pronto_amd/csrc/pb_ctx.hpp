@@ -1,6 +1,8 @@
 // pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so
-// (the kernels are instantiated in several .hip files so that they compile in parallel: pb_step.hip the step kernels,
-// pb_update15.hip / pb_update21.hip the generic update kernels, pb_smooth.hip the smoother, pronto_batch.hip the rest).
+// (the kernels are instantiated in fourteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip
+// and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
+// pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip; pb_yawlock.hip;
+// pronto_batch.hip the C ABI and the rest).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -74,7 +76,7 @@ struct pb_ctx {
   // IMU front end per filter (pb_ins_body_block, rbis_frontend.hpp): last body-frame sample [6][stride], previous message time [stride]
   double *ins_last = nullptr;
   int64_t *ins_prev_ut = nullptr;
-  const uint8_t *imu_valid_next = nullptr;   // pb_set_imu_valid: one-shot, taken by the next call that takes an IMU step ...
+  const uint8_t *imu_valid_next = nullptr;   // pb_set_imu_valid: one-shot, taken by the next call that takes an IMU step (Call, pronto_batch.hip) ...
   const uint8_t *imu_valid_cur = nullptr;    // ... and held here for the duration of that call
   double *imu_keep = nullptr;                // [7][stride]: the IMU block that call's step kernel reads instead (pbk_idle_prepare)
   // chunked uploads (pb_upload_async): fences recorded on the main stream, one event for "the uploads issued so far"
@@ -178,7 +180,7 @@ int pbk_step_pred_kernel(pb_ctx *c, double *out, double *pred, const double *imu
 int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                      const double *z2, const double *r2, const double *rb2, const double *qm2, const uint8_t *mask2,
                      const StepBcast *bcast = nullptr, const double *zb = nullptr, const double *qb = nullptr);
-// pb_update15.hip / pb_update21.hip: generic indexed (+ orientation, qm != NULL) update, m = 1..6
+// pb_update.hip (15 states) / pb_update_rt21.hip: generic indexed (+ orientation, qm != NULL) update, m = 1..6
 int pbk_update15(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb,
                  const double *qm, const uint8_t *mask);
 int pbk_update21(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb,

@@ -1,24 +1,40 @@
 // pb_step.hip -- launchers of the step kernels (k_step, k_step_coop, k_replay_fused); see pb_ctx.hpp.
+#include <type_traits>
+
 #include "pb_ctx.hpp"
 
+// the cache policy of the state round trip (MemHint, chosen in pb_create from the state size) as a compile-time constant: f(MH)
+template <class F>
+static void with_mem_hint(int mem_hint, F f)
+{
+  switch (mem_hint) {
+  case MH_STORE_SC1: f(std::integral_constant<int, MH_STORE_SC1>()); break;
+  case MH_STREAM_NT: f(std::integral_constant<int, MH_STREAM_NT>()); break;
+  default: f(std::integral_constant<int, MH_DEFAULT>()); break;
+  }
+}
+
+// The ONE launch of the step kernel this context runs: from `st` into `out`, a grid that covers nb filters (the inputs stay blocks
+// [rows][B] of the whole batch: the kernels take B as the row stride).  half: two workgroups per tile -- the whole-batch 15-state
+// cooperative launch only.
 template <bool UPDATE, int MH>
-static void launch_step_mh(pb_ctx *c, double *out, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
-                           const StepBcast &bc)
+static void launch_step_kernel(pb_ctx *c, const double *st, double *out, int nb, bool coop15, bool half, const double *imu, const double *lo,
+                               const uint8_t *mask, const double q[4], const StepBcast &bc)
 {
   const int B = c->B;
-  if (c->ns == 15 && c->coop15) {
+  if (c->ns == 15 && coop15) {
     Consts kk = c->k;
-    kk.half_tiles = c->half15 ? 1 : 0;   // (this launch only: every other kernel that takes c->k keeps whole tiles)
-    k_step_coop<15, UPDATE, MH><<<nblk(B) * (c->half15 ? 2 : 1), 128, 0, c->stream>>>(c->st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, CorrArgs(), bc);
+    kk.half_tiles = half ? 1 : 0;   // (this launch only: every other kernel that takes c->k keeps whole tiles)
+    k_step_coop<15, UPDATE, MH><<<nblk(nb) * (half ? 2 : 1), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, CorrArgs(), bc);
   } else if (c->ns == 15) {
-    k_step<15, UPDATE, MH><<<(B + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(c->st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    k_step<15, UPDATE, MH><<<(nb + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
   } else if (c->quad21) {
     // n = 21: 231 packed covariance entries do not fit one lane's registers; four cooperating waves per tile at two waves
     // per SIMD (rbis_quad.hpp): one launch, one state round trip.
-    k_step_quad<UPDATE, MH><<<nblk(B), 256, 0, c->stream>>>(c->st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    k_step_quad<UPDATE, MH><<<nblk(nb), 256, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
   } else {
     // the two-wave cooperative kernel at one wave per SIMD (rbis_coop.hpp); PRONTO_BATCH_QUAD21=0
-    k_step_coop<21, UPDATE, MH><<<nblk(B), 128, 0, c->stream>>>(c->st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, CorrArgs(), bc);
+    k_step_coop<21, UPDATE, MH><<<nblk(nb), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, CorrArgs(), bc);
   }
 }
 
@@ -29,43 +45,27 @@ static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uin
   int rc = PB_OK;
   imu = pbk_idle_prepare(c, imu, &rc);
   if (rc) return rc;
-  switch (c->mem_hint) {  // cache policy of the state round trip, chosen in pb_create from the state size
-  case MH_STORE_SC1: launch_step_mh<UPDATE, MH_STORE_SC1>(c, out, imu, lo, mask, q, bc); break;
-  case MH_STREAM_NT: launch_step_mh<UPDATE, MH_STREAM_NT>(c, out, imu, lo, mask, q, bc); break;
-  default: launch_step_mh<UPDATE, MH_DEFAULT>(c, out, imu, lo, mask, q, bc); break;
-  }
+  with_mem_hint(c->mem_hint, [&](auto mh) {
+    launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->coop15, c->half15, imu, lo, mask, q, bc);
+  });
   LAUNCHCHK(c);
   update_done(c, out);
   return PB_OK;
 }
 
-
 // The fused step on the filters [b0, b0 + nb) only -- b0 and the batch multiples of 64 (whole tiles), the posterior in place, the inputs
-// still blocks [rows][B] of the WHOLE batch (the kernels take B as the row stride; the block is addressed by shifting every pointer).
+// still blocks [rows][B] of the WHOLE batch (the block is addressed by shifting every pointer).
 // coop15 / mem_hint are the caller's: a block that fits the memory-side cache wants the kernel and the cache policy of ITS size.
-template <int MH>
-static void launch_range_mh(pb_ctx *c, double *st, const double *imu, const double *lo, const uint8_t *mask, const double q[4], int nb, bool coop15)
-{
-  const int B = c->B;
-  const StepBcast bc = StepBcast();
-  if (c->ns == 15 && coop15) k_step_coop<15, true, MH><<<nblk(nb), 128, 0, c->stream>>>(st, st, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, CorrArgs(), bc);
-  else if (c->ns == 15) k_step<15, true, MH><<<(nb + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(st, st, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
-  else if (c->quad21) k_step_quad<true, MH><<<nblk(nb), 256, 0, c->stream>>>(st, st, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
-  else k_step_coop<21, true, MH><<<nblk(nb), 128, 0, c->stream>>>(st, st, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, CorrArgs(), bc);
-}
 int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, bool coop15, int mem_hint)
 {
   if (c->st != c->st_base || c->out_slot >= 0 || (c->B & 63) || (b0 & 63) || (nb & 63) || b0 + nb > c->B)
     return fail(c, PB_ERR_STATE, "pbk_step_range: whole tiles of a head that lives in the context's own array");
   const size_t tile_doubles = c->state_doubles / (size_t) (c->stride / 64);
   double *st = c->st + (size_t) (b0 / 64) * tile_doubles;
-  const double *imu_b = imu + b0, *lo_b = lo + b0;
   const uint8_t *mask_b = mask ? mask + b0 : nullptr;
-  switch (mem_hint) {
-  case MH_STORE_SC1: launch_range_mh<MH_STORE_SC1>(c, st, imu_b, lo_b, mask_b, q, nb, coop15); break;
-  case MH_STREAM_NT: launch_range_mh<MH_STREAM_NT>(c, st, imu_b, lo_b, mask_b, q, nb, coop15); break;
-  default: launch_range_mh<MH_DEFAULT>(c, st, imu_b, lo_b, mask_b, q, nb, coop15); break;
-  }
+  with_mem_hint(mem_hint, [&](auto mh) {
+    launch_step_kernel<true, decltype(mh)::value>(c, st, st, nb, coop15, false, imu + b0, lo + b0, mask_b, q, StepBcast());
+  });
   LAUNCHCHK(c);
   return PB_OK;
 }
@@ -157,17 +157,6 @@ static void launch_corr(pb_ctx *c, double *out, const double *imu, const double 
 {
   k_step_coop<NS, true, MH, CORR><<<nblk(c->B), 128, 0, c->stream>>>(c->st, out, c->B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, ca, bc);
 }
-template <int NS, class CORR>
-static void launch_corr_mh(pb_ctx *c, double *out, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
-                           const CorrArgs &ca, const StepBcast &bc)
-{
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: launch_corr<NS, MH_STORE_SC1, CORR>(c, out, imu, lo, mask, q, ca, bc); break;
-  case MH_STREAM_NT: launch_corr<NS, MH_STREAM_NT, CORR>(c, out, imu, lo, mask, q, ca, bc); break;
-  default: launch_corr<NS, MH_DEFAULT, CORR>(c, out, imu, lo, mask, q, ca, bc); break;
-  }
-}
-
 int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                      const double *z2, const double *r2, const double *rb2, const double *qm2, const uint8_t *mask2,
                      const StepBcast *bcast, const double *zb, const double *qb)
@@ -203,8 +192,10 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
   int rc = PB_OK;
   imu = pbk_idle_prepare(c, imu, &rc);
   if (rc) return rc;
-  if (corr_kind == PB_CORR_POS_ORIENT) launch_corr_mh<15, CorrPosOrient>(c, out, imu, lo, mask, q, ca, bc);
-  else launch_corr_mh<15, CorrPosYaw>(c, out, imu, lo, mask, q, ca, bc);
+  with_mem_hint(c->mem_hint, [&](auto mh) {
+    if (corr_kind == PB_CORR_POS_ORIENT) launch_corr<15, decltype(mh)::value, CorrPosOrient>(c, out, imu, lo, mask, q, ca, bc);
+    else launch_corr<15, decltype(mh)::value, CorrPosYaw>(c, out, imu, lo, mask, q, ca, bc);
+  });
   LAUNCHCHK(c);
   update_done(c, out);
   return PB_OK;

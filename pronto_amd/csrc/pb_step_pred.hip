@@ -9,7 +9,7 @@ static int launch_pred_mh(pb_ctx *c, double *out, double *pred, const double *im
   const int B = c->B;
   if (c->ns == 15 && c->coop15) {
     Consts kk = c->k;
-    kk.half_tiles = c->half15 ? 1 : 0;   // (as launch_step_mh: this launch only)
+    kk.half_tiles = c->half15 ? 1 : 0;   // (as launch_step_kernel: this launch only)
     k_step_coop_pred<15, MH><<<nblk(B) * (c->half15 ? 2 : 1), 128, 0, c->stream>>>(c->st, out, pred, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, bc);
     return PB_OK;
   }

@@ -343,7 +343,7 @@ static int stage_reserve(pb_ctx *c, size_t bytes)
   return PB_OK;
 }
 
-// Resolve up to 4 caller buffers: device pointers pass through; host buffers are packed into the staging area.
+// Resolve the caller buffers of one call (up to 7: pb_step_legodo_correct): device pointers pass through; host buffers are packed into the staging area.
 struct Part {
   const void *src;
   size_t bytes;
@@ -411,17 +411,73 @@ static int stage_in(pb_ctx *c, int mem, Part *parts, int n)
   return PB_OK;
 }
 
-#define ENTER(c)                                       \
-  if (!(c)) return PB_ERR_ARG;                         \
-  HIPCHK((c), hipSetDevice((c)->dev))
+// ---- the per-call contract: what an entry point takes from the context, declared in ONE line at its top -- CALL(c, flags) ----
+// The one-shot inputs belong to the NEXT call that takes them, whatever becomes of it: the pb_set_imu_valid mask to the next call that
+// takes an IMU step, the per-filter message times / validity (pb_legodo_set_message_times) to the next odometry or pair call,
+// pb_set_pred_slot to the next pb_step_legodo / pb_step_legodo_split.  The guard takes them FIRST, before anything is validated, so
+// that a call that fails early cannot leave them behind for an unrelated later call, and forgets them when the call returns.
+enum : unsigned {
+  IMU_STEP = 1,      // takes the IMU validity mask: held in imu_valid_cur for the duration of the call (pbk_idle_prepare)
+  LEG_TIMES = 2,     // takes the message times / validity (Call::times)
+  PRED_TAKE = 4,     // writes a predicted posterior: consumes a pending predicted slot, whatever becomes of the call
+  PRED_REFUSE = 8,   // takes an IMU step or an update but writes no predicted posterior: with a slot pending it refuses and forgets it
+  PRED_FORGET = 16,  // runs a whole log of steps with predicted slots of its own: a pending one is forgotten
+  NEEDS_STATE = 32,  // PB_ERR_STATE before pb_reset
+};
+struct LegMsgTimes {
+  const int64_t *utimes = nullptr;
+  const uint8_t *valid = nullptr;
+};
+struct Call {
+  pb_ctx *const c;
+  const unsigned what;
+  LegMsgTimes times;
+  int rc;
+  Call(pb_ctx *ctx, const char *fn, unsigned flags) : c(ctx), what(flags) { rc = enter(fn); }
+  Call(const Call &) = delete;
+  ~Call()
+  {
+    if (!c) return;
+    if (what & IMU_STEP) c->imu_valid_cur = nullptr;
+    if (what & PRED_TAKE) c->pred_slot = -1;
+  }
 
-#define NEED_STATE(c) \
-  if (!(c)->have_state) return fail((c), PB_ERR_STATE, "%s before pb_reset", __func__)
+ private:
+  int enter(const char *fn)
+  {
+    if (!c) return PB_ERR_ARG;
+    if (what & IMU_STEP) {
+      c->imu_valid_cur = c->imu_valid_next;
+      c->imu_valid_next = nullptr;
+    }
+    if (what & LEG_TIMES) {
+      if (c->leg_ut_on) times.utimes = c->leg_ut_ext ? c->leg_ut_ext : c->leg_ut;
+      if (c->leg_valid_on) times.valid = c->leg_valid_ext ? c->leg_valid_ext : c->leg_valid;
+      c->leg_ut_on = c->leg_valid_on = false;
+      c->leg_ut_ext = nullptr;
+      c->leg_valid_ext = nullptr;
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    if ((what & (PRED_REFUSE | PRED_FORGET)) && c->pred_slot >= 0) {
+      c->pred_slot = -1;
+      if (what & PRED_REFUSE)
+        return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / pb_step_legodo_split)", fn);
+    }
+    if ((what & NEEDS_STATE) && !c->have_state) return fail(c, PB_ERR_STATE, "%s before pb_reset", fn);
+    // the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
+    if ((what & PRED_TAKE) && c->pred_slot >= 0 && (c->pred_slot >= c->nhist || c->pred_slot == c->out_slot || c->pred_slot == pb_head_slot(c)))
+      return fail(c, PB_ERR_ARG, "predicted slot %d: out of range, the output slot or the head's slot", c->pred_slot);
+    return PB_OK;
+  }
+};
+#define CALL(c, flags)               \
+  Call call((c), __func__, (flags)); \
+  if (call.rc) return call.rc
 
 
 extern "C" int pb_reset(pb_ctx *c, const double *vec, const double *quat, const double *cov, int broadcast, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!vec || !quat || !cov) return fail(c, PB_ERR_ARG, "pb_reset: NULL input");
   c->st = c->st_base;  // a reset always lands in the context's own array (a checkpoint the head lived in stays intact)
   c->out_slot = -1;
@@ -459,8 +515,7 @@ extern "C" int pb_reset(pb_ctx *c, const double *vec, const double *quat, const 
 // reference's updateFilter(prior_state, prior_cov, prior_loglikelihood) contract, rbis_update_interface.hpp:14-35) becomes the head.
 extern "C" int pb_set_head(pb_ctx *c, const double *vec, const double *quat, const double *cov, const double *loglik, int mem)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (!vec || !quat || !cov) return fail(c, PB_ERR_ARG, "pb_set_head: NULL input");
   if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_set_head: mem must be PB_HOST or PB_DEVICE");
   const int n = c->ns, B = c->B;
@@ -487,23 +542,8 @@ extern "C" int pb_set_imu_valid(pb_ctx *c, const uint8_t *valid_dev)
   c->imu_valid_next = valid_dev;
   return PB_OK;
 }
-// The mask belongs to the NEXT call that takes an IMU step, whatever becomes of it: such an entry point moves it from imu_valid_next to
-// imu_valid_cur first thing (ImuIdleTake) and forgets it when it returns; the launchers of the step kernels (pb_step.hip) pass
-// their IMU block through pbk_idle_prepare right in front of their ONE launch (rbis_frontend.hpp, k_imu_idle_prepare).
-struct ImuIdleTake {
-  pb_ctx *c;
-  explicit ImuIdleTake(pb_ctx *ctx) : c(ctx)
-  {
-    if (c) {
-      c->imu_valid_cur = c->imu_valid_next;
-      c->imu_valid_next = nullptr;
-    }
-  }
-  ~ImuIdleTake()
-  {
-    if (c) c->imu_valid_cur = nullptr;
-  }
-};
+// The call that takes the mask (CALL: IMU_STEP) holds it in imu_valid_cur; the launchers of the step kernels (pb_step.hip) pass their
+// IMU block through pbk_idle_prepare right in front of their ONE launch (rbis_frontend.hpp, k_imu_idle_prepare).
 const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out)
 {
   *rc_out = PB_OK;
@@ -524,126 +564,94 @@ const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out)
   return c->imu_keep;
 }
 
-// pb_set_pred_slot belongs to the next pb_step_legodo / pb_step_legodo_split, and that call consumes it whatever becomes of it
-// (PredTake).  The other entry points that take an IMU step or an update do not write a predicted posterior: with one pending
-// they refuse and forget it (refuse_pred).
-struct PredTake {
-  pb_ctx *c;
-  explicit PredTake(pb_ctx *ctx) : c(ctx) {}
-  ~PredTake()
-  {
-    if (c) c->pred_slot = -1;
-  }
-};
-static int refuse_pred(pb_ctx *c, const char *fn)
+// The IMU block of a call, resolved.  PB_HOST_BROADCAST -- one message for every filter -- travels as kernel arguments (bc; p[0].dev
+// stays NULL): no device block, no fill launch, no input traffic.  A block in any other space goes through stage_in as p[0], in the
+// same call as the n - 1 parts the caller put behind it because they live in the same space (the double-buffered host staging must
+// not be flipped twice before its consumer is enqueued).
+static int imu_in(pb_ctx *c, const double *imu_block, int imu_mem, StepBcast &bc, Part *p, int n = 1)
 {
-  if (!c || c->pred_slot < 0) return PB_OK;
-  c->pred_slot = -1;
-  return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / pb_step_legodo_split)", fn);
+  p[0] = Part{ imu_block, sizeof(double) * 7 * c->B, nullptr };
+  if (imu_mem != PB_HOST_BROADCAST) return stage_in(c, imu_mem, p, n);
+  memcpy(bc.imu, imu_block, sizeof(bc.imu));
+  bc.on |= 1;
+  return PB_OK;
 }
-// the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
-static int check_pred(pb_ctx *c)
+// the same block for the odometry kernel, which runs the IMU step ahead of itself
+static LegAhead leg_ahead(const StepBcast &bc, const double *d_imu)
 {
-  if (c->pred_slot < 0) return PB_OK;
-  if (c->pred_slot >= c->nhist || c->pred_slot == c->out_slot || c->pred_slot == pb_head_slot(c))
-    return fail(c, PB_ERR_ARG, "predicted slot %d: out of range, the output slot or the head's slot", c->pred_slot);
+  LegAhead ah;
+  ah.on = 1;
+  ah.bcast = bc.on & 1;
+  memcpy(ah.v, bc.imu, sizeof(ah.v));
+  ah.imu = d_imu;
+  return ah;
+}
+
+// the frame of a timed entry point: device time between the two events (elapsed_ms NULL: not timed, no event)
+static int timed_begin(pb_ctx *c, const float *elapsed_ms)
+{
+  if (elapsed_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  return PB_OK;
+}
+static int timed_end(pb_ctx *c, float *elapsed_ms)
+{
+  if (!elapsed_ms) return PB_OK;
+  HIPCHK(c, hipEventRecord(c->ev1, c->stream));
+  HIPCHK(c, hipEventSynchronize(c->ev1));
+  HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
   return PB_OK;
 }
 
 extern "C" int pb_predict(pb_ctx *c, const double *imu_block, const double q[4], int mem)
 {
-  ImuIdleTake idle(c);
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_predict")) return rc;
-  NEED_STATE(c);
+  CALL(c, IMU_STEP | PRED_REFUSE | NEEDS_STATE);
   if (!imu_block || !q) return fail(c, PB_ERR_ARG, "pb_predict: NULL input");
-  if (mem == PB_HOST_BROADCAST) {  // one message for every filter: the 7 values are kernel arguments
-    StepBcast bc;
-    memcpy(bc.imu, imu_block, sizeof(bc.imu));
-    bc.on = 1;
-    return pbk_step(c, false, nullptr, nullptr, nullptr, q, &bc);
+  StepBcast bc;
+  Part p[1];
+  if (int rc = imu_in(c, imu_block, mem, bc, p)) return rc;
+  return pbk_step(c, false, (const double *) p[0].dev, nullptr, nullptr, q, &bc);
+}
+
+// The fused step with its two input groups (the IMU block; the measurement and its mask) each in a space of its own.  At most one
+// of the two goes through the double-buffered host staging (PB_HOST) -- in ONE call when both live there; a broadcast group
+// travels as kernel arguments (a parameter sweep replaying one robot's log), a device group is read in place.
+static int step_legodo_impl(pb_ctx *c, const char *who, const double *imu_block, int imu_mem, const double *lo_block, const uint8_t *mask,
+                            int lo_mem, const double q[4])
+{
+  if (!imu_block || !lo_block || !q) return fail(c, PB_ERR_ARG, "%s: NULL input", who);
+  const bool together = imu_mem == lo_mem;
+  StepBcast bc;
+  Part p[3] = { {}, { lo_block, sizeof(double) * 6 * c->B, nullptr }, { mask, (size_t) c->B, nullptr } };
+  if (int rc = imu_in(c, imu_block, imu_mem, bc, p, together ? 3 : 1)) return rc;
+  if (lo_mem == PB_HOST_BROADCAST) {
+    if (mask) return fail(c, PB_ERR_ARG, "PB_HOST_BROADCAST: a mask cannot be broadcast (pass mask = NULL)");
+    memcpy(bc.lo, lo_block, sizeof(bc.lo));
+    bc.on |= 2;
+  } else if (!together) {
+    if (int rc = stage_in(c, lo_mem, p + 1, 2)) return rc;
   }
-  Part p[1] = { { imu_block, sizeof(double) * 7 * c->B, 0 } };
-  int rc = stage_in(c, mem, p, 1);
-  if (rc) return rc;
-  return pbk_step(c, false, (const double *) p[0].dev, nullptr, nullptr, q);
+  return pbk_step(c, true, (const double *) p[0].dev, (const double *) p[1].dev, (const uint8_t *) p[2].dev, q, &bc);
 }
 
 extern "C" int pb_step_legodo(pb_ctx *c, const double *imu_block, const double *lo_block, const uint8_t *mask,
                               const double q[4], int mem)
 {
-  ImuIdleTake idle(c);
-  PredTake pred(c);
-  ENTER(c);
-  NEED_STATE(c);
-  if (int rc = check_pred(c)) return rc;
-  if (!imu_block || !lo_block || !q) return fail(c, PB_ERR_ARG, "pb_step_legodo: NULL input");
-  if (mem == PB_HOST_BROADCAST) {
-    // one message for every filter (a parameter sweep replaying one robot's log): the 13 values are kernel arguments --
-    // no device block, no fill launch, no input traffic.  A mask cannot be broadcast.
-    if (mask) return fail(c, PB_ERR_ARG, "PB_HOST_BROADCAST: a mask cannot be broadcast (pass mask = NULL)");
-    StepBcast bc;
-    memcpy(bc.imu, imu_block, sizeof(bc.imu));
-    memcpy(bc.lo, lo_block, sizeof(bc.lo));
-    bc.on = 3;
-    return pbk_step(c, true, nullptr, nullptr, nullptr, q, &bc);
-  }
-  Part p[3] = { { imu_block, sizeof(double) * 7 * c->B, 0 }, { lo_block, sizeof(double) * 6 * c->B, 0 },
-                { mask, (size_t) c->B, 0 } };
-  int rc = stage_in(c, mem, p, 3);
-  if (rc) return rc;
-  return pbk_step(c, true, (const double *) p[0].dev, (const double *) p[1].dev, (const uint8_t *) p[2].dev, q);
+  CALL(c, IMU_STEP | PRED_TAKE | NEEDS_STATE);
+  return step_legodo_impl(c, "pb_step_legodo", imu_block, mem, lo_block, mask, mem, q);
 }
 
 extern "C" int pb_step_legodo_split(pb_ctx *c, const double *imu_block, int imu_mem, const double *lo_block,
                                     const uint8_t *mask, int lo_mem, const double q[4])
 {
-  // (the same space: pb_step_legodo takes the pb_set_imu_valid mask and a predicted slot itself -- hand the call on BEFORE taking the
-  // mask here, or its own ImuIdleTake would find it gone)
-  if (imu_mem == lo_mem) return pb_step_legodo(c, imu_block, lo_block, mask, q, imu_mem);
-  ImuIdleTake idle(c);
-  PredTake pred(c);
-  ENTER(c);
-  NEED_STATE(c);
-  if (int rc = check_pred(c)) return rc;
-  if (!imu_block || !lo_block || !q) return fail(c, PB_ERR_ARG, "pb_step_legodo_split: NULL input");
-  if (imu_mem == PB_HOST && lo_mem == PB_HOST) return fail(c, PB_ERR_ARG, "pb_step_legodo_split: unreachable");
-  StepBcast bc;
-  const double *d_imu = nullptr, *d_lo = nullptr;
-  const uint8_t *d_mask = nullptr;
-  // at most one of the two groups goes through the double-buffered host staging (PB_HOST); a broadcast group travels as
-  // kernel arguments, a device group is read in place
-  if (imu_mem == PB_HOST_BROADCAST) {
-    memcpy(bc.imu, imu_block, sizeof(bc.imu));
-    bc.on |= 1;
-  } else {
-    Part p[1] = { { imu_block, sizeof(double) * 7 * c->B, 0 } };
-    int rc = stage_in(c, imu_mem, p, 1);
-    if (rc) return rc;
-    d_imu = (const double *) p[0].dev;
-  }
-  if (lo_mem == PB_HOST_BROADCAST) {
-    if (mask) return fail(c, PB_ERR_ARG, "PB_HOST_BROADCAST: a mask cannot be broadcast (pass mask = NULL)");
-    memcpy(bc.lo, lo_block, sizeof(bc.lo));
-    bc.on |= 2;
-  } else {
-    Part p[2] = { { lo_block, sizeof(double) * 6 * c->B, 0 }, { mask, (size_t) c->B, 0 } };
-    int rc = stage_in(c, lo_mem, p, 2);
-    if (rc) return rc;
-    d_lo = (const double *) p[0].dev;
-    d_mask = (const uint8_t *) p[1].dev;
-  }
-  return pbk_step(c, true, d_imu, d_lo, d_mask, q, &bc);
+  CALL(c, IMU_STEP | PRED_TAKE | NEEDS_STATE);
+  return step_legodo_impl(c, "pb_step_legodo_split", imu_block, imu_mem, lo_block, mask, lo_mem, q);
 }
 
 extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const double *lo_block, const uint8_t *mask,
                                       const double q[4], int mem, int corr_kind, const double *z2, const double *R2,
                                       int r_kind2, const double *quat_meas2, const uint8_t *mask2, int mem2)
 {
-  ImuIdleTake idle(c);
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_step_legodo_correct")) return rc;
-  NEED_STATE(c);
+  CALL(c, IMU_STEP | PRED_REFUSE | NEEDS_STATE);
   if (!imu_block || !lo_block || !q || !z2 || !R2 || !quat_meas2) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: NULL input");
   if (corr_kind != PB_CORR_POS_ORIENT && corr_kind != PB_CORR_POS_YAW) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: bad corr_kind %d", corr_kind);
   if (mem2 == PB_HOST_BROADCAST && r_kind2 == PB_R_DIAG) r_kind2 = PB_R_DIAG_BROADCAST;
@@ -654,17 +662,17 @@ extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const 
   // (the two-wave 21-state mapping, PRONTO_BATCH_QUAD21=0, has no m = 6 kernel that takes z / quat_meas as arguments:
   // its correction falls back to the generic update, which needs the replicated blocks staged below)
   const bool arg_kernel = c->ns == 15 || c->quad21 || m2 <= 4;
-  if (mem == PB_HOST_BROADCAST && mem2 == PB_HOST_BROADCAST && rbc && !mask && !mask2 && arg_kernel) {
-    // one robot's three messages for every filter: everything travels as kernel arguments
-    StepBcast bc;
-    memcpy(bc.imu, imu_block, sizeof(bc.imu));
-    memcpy(bc.lo, lo_block, sizeof(bc.lo));
-    bc.on = 3;
-    return pbk_step_correct(c, corr_kind, nullptr, nullptr, nullptr, q, nullptr, nullptr, R2, nullptr, nullptr, &bc, z2, quat_meas2);
-  }
   Part p[7] = { { imu_block, sizeof(double) * 7 * B, 0 }, { lo_block, sizeof(double) * 6 * B, 0 }, { mask, B, 0 },
                 { z2, sizeof(double) * m2 * B, 0 }, { rbc ? nullptr : R2, rbc ? 0 : sizeof(double) * m2 * B, 0 },
                 { quat_meas2, sizeof(double) * 4 * B, 0 }, { mask2, B, 0 } };
+  if (mem == PB_HOST_BROADCAST && mem2 == PB_HOST_BROADCAST && rbc && !mask && !mask2 && arg_kernel) {
+    // one robot's three messages for every filter: everything travels as kernel arguments
+    StepBcast bc;
+    (void) imu_in(c, imu_block, mem, bc, p);
+    memcpy(bc.lo, lo_block, sizeof(bc.lo));
+    bc.on |= 2;
+    return pbk_step_correct(c, corr_kind, nullptr, nullptr, nullptr, q, nullptr, nullptr, R2, nullptr, nullptr, &bc, z2, quat_meas2);
+  }
   // one staging call when both groups live in the same space (the double-buffered host staging must not be flipped twice
   // before its consumer is enqueued); otherwise at most one of the two groups is PB_HOST
   int rc;
@@ -682,9 +690,7 @@ extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const 
 extern "C" int pb_run_legodo(pb_ctx *c, int n_steps, const double *imu_stream, const double *lo_stream,
                              const uint8_t *mask_stream, const double q[4], float *elapsed_ms)
 {
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_run_legodo")) return rc;
-  NEED_STATE(c);
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
   if (n_steps < 0 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_run_legodo: bad argument");
   const size_t B = (size_t) c->B;
   // Experiment switch: PRONTO_BATCH_GRAPH=1 captures the n_steps launches into a HIP graph and times
@@ -710,7 +716,7 @@ extern "C" int pb_run_legodo(pb_ctx *c, int n_steps, const double *imu_stream, c
     (void) hipGraphDestroy(graph);
     return PB_OK;
   }
-  if (elapsed_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
+  if (int rc = timed_begin(c, elapsed_ms)) return rc;
   if (c->run_block > 0 && n_steps > 1 && c->st == c->st_base && c->out_slot < 0) {
     // cache-blocked order (pb_create): every block of filters runs the whole stream before the next block starts
     for (long b0 = 0; b0 < (long) B; b0 += c->run_block) {
@@ -728,79 +734,49 @@ extern "C" int pb_run_legodo(pb_ctx *c, int n_steps, const double *imu_stream, c
       if (rc) return rc;
     }
   }
-  if (elapsed_ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
+  return timed_end(c, elapsed_ms);
+}
+
+// write_through: the posterior of step t also goes to checkpoint slot first_slot + t
+static int replay_impl(pb_ctx *c, const char *who, int n_steps, int steps_per_launch, const double *imu_stream, const double *lo_stream,
+                       const uint8_t *mask_stream, const double q[4], bool write_through, int first_slot, float *elapsed_ms)
+{
+  if (n_steps < 0 || steps_per_launch < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "%s: bad argument", who);
+  if (write_through && (first_slot < 0 || first_slot + n_steps > c->nhist))
+    return fail(c, PB_ERR_ARG, "%s: slots %d..%d of %d (pb_history_reserve)", who, first_slot, first_slot + n_steps - 1, c->nhist);
+  const size_t B = (size_t) c->B;
+  // this kernel works in place, never on a checkpoint slot: the state rides in registers from the context's own array, the slots
+  // only receive copies
+  if (int rc = detach_head(c, true)) return rc;
+  if (int rc = timed_begin(c, elapsed_ms)) return rc;
+  for (int s = 0; s < n_steps; s += steps_per_launch) {
+    const int T = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
+    int rc = pbk_replay_fused(c, T, imu_stream + (size_t) s * 7 * B, lo_stream + (size_t) s * 6 * B,
+                              mask_stream ? mask_stream + (size_t) s * B : nullptr, q, write_through ? first_slot + s : -1);
+    if (rc) return rc;
   }
-  return PB_OK;
+  return timed_end(c, elapsed_ms);
 }
 
 extern "C" int pb_replay_legodo_fused(pb_ctx *c, int n_steps, int steps_per_launch, const double *imu_stream,
                                       const double *lo_stream, const uint8_t *mask_stream, const double q[4],
                                       float *elapsed_ms)
 {
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_replay_legodo_fused")) return rc;
-  NEED_STATE(c);
-  if (n_steps < 0 || steps_per_launch < 1 || !imu_stream || !lo_stream || !q)
-    return fail(c, PB_ERR_ARG, "pb_replay_legodo_fused: bad argument");
-  const size_t B = (size_t) c->B;
-  {
-    int rc = detach_head(c, true);  // this kernel works in place: never on a checkpoint slot
-    if (rc) return rc;
-  }
-  if (elapsed_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  for (int s = 0; s < n_steps; s += steps_per_launch) {
-    const int T = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
-    int rc = pbk_replay_fused(c, T, imu_stream + (size_t) s * 7 * B, lo_stream + (size_t) s * 6 * B,
-                              mask_stream ? mask_stream + (size_t) s * B : nullptr, q);
-    if (rc) return rc;
-  }
-  if (elapsed_ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
-  }
-  return PB_OK;
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
+  return replay_impl(c, "pb_replay_legodo_fused", n_steps, steps_per_launch, imu_stream, lo_stream, mask_stream, q, false, -1, elapsed_ms);
 }
 
 extern "C" int pb_replay_legodo_checkpointed(pb_ctx *c, int n_steps, int steps_per_launch, const double *imu_stream,
                                              const double *lo_stream, const uint8_t *mask_stream, const double q[4], int first_slot,
                                              float *elapsed_ms)
 {
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_replay_legodo_checkpointed")) return rc;
-  NEED_STATE(c);
-  if (n_steps < 0 || steps_per_launch < 1 || !imu_stream || !lo_stream || !q)
-    return fail(c, PB_ERR_ARG, "pb_replay_legodo_checkpointed: bad argument");
-  if (first_slot < 0 || first_slot + n_steps > c->nhist)
-    return fail(c, PB_ERR_ARG, "pb_replay_legodo_checkpointed: slots %d..%d of %d (pb_history_reserve)", first_slot, first_slot + n_steps - 1, c->nhist);
-  const size_t B = (size_t) c->B;
-  {
-    int rc = detach_head(c, true);  // the state rides in registers from the context's own array; the slots only receive copies
-    if (rc) return rc;
-  }
-  if (elapsed_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  for (int s = 0; s < n_steps; s += steps_per_launch) {
-    const int T = (n_steps - s < steps_per_launch) ? n_steps - s : steps_per_launch;
-    int rc = pbk_replay_fused(c, T, imu_stream + (size_t) s * 7 * B, lo_stream + (size_t) s * 6 * B,
-                              mask_stream ? mask_stream + (size_t) s * B : nullptr, q, first_slot + s);
-    if (rc) return rc;
-  }
-  if (elapsed_ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
-  }
-  return PB_OK;
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
+  return replay_impl(c, "pb_replay_legodo_checkpointed", n_steps, steps_per_launch, imu_stream, lo_stream, mask_stream, q, true, first_slot, elapsed_ms);
 }
 
 static int update_common(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind,
                          const double *qm, bool orient, const uint8_t *mask, int mem)
 {
-  ENTER(c);
-  NEED_STATE(c);
   if (m < 1 || m > 6) return fail(c, PB_ERR_ARG, "update: m must be 1..6 (got %d)", m);
   if (!idx || !z || !R) return fail(c, PB_ERR_ARG, "update: NULL input");
   if (orient && !qm) return fail(c, PB_ERR_ARG, "update: quat_meas is NULL");
@@ -849,21 +825,20 @@ static int update_common(pb_ctx *c, int m, const int *idx, const double *z, cons
 extern "C" int pb_update_indexed(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int r_kind,
                                  const uint8_t *mask, int mem)
 {
-  if (int rc = refuse_pred(c, "pb_update_indexed")) return rc;
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
   return update_common(c, m, idx, z, R, r_kind, nullptr, false, mask, mem);
 }
 
 extern "C" int pb_update_indexed_orient(pb_ctx *c, int m, const int *idx, const double *z, const double *R,
                                         int r_kind, const double *quat_meas, const uint8_t *mask, int mem)
 {
-  if (int rc = refuse_pred(c, "pb_update_indexed_orient")) return rc;
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
   return update_common(c, m, idx, z, R, r_kind, quat_meas, true, mask, mem);
 }
 
 extern "C" int pb_snapshot(pb_ctx *c, int slot)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (slot < 0 || slot >= c->nsnap) return fail(c, PB_ERR_STATE, "pb_snapshot: slot %d of %d", slot, c->nsnap);
   double *snap = c->snaps + (size_t) slot * 7 * c->stride;
   if (c->ns == 15) k_snapshot<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->stride, c->B, snap);
@@ -874,7 +849,7 @@ extern "C" int pb_snapshot(pb_ctx *c, int slot)
 
 extern "C" int pb_snapshot_from_slot(pb_ctx *c, int slot, int checkpoint_slot)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (slot < 0 || slot >= c->nsnap) return fail(c, PB_ERR_STATE, "pb_snapshot_from_slot: slot %d of %d", slot, c->nsnap);
   if (checkpoint_slot < 0 || checkpoint_slot >= c->nhist)
     return fail(c, PB_ERR_STATE, "pb_snapshot_from_slot: checkpoint slot %d of %d", checkpoint_slot, c->nhist);
@@ -889,7 +864,7 @@ extern "C" int pb_snapshot_from_slot(pb_ctx *c, int slot, int checkpoint_slot)
 extern "C" int pb_compose_delta(pb_ctx *c, int slot, const double *t, const double *q, double *z_out,
                                 double *quat_out, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (slot < 0 || slot >= c->nsnap) return fail(c, PB_ERR_STATE, "pb_compose_delta: slot %d of %d", slot, c->nsnap);
   if (!t || !q || !z_out || !quat_out) return fail(c, PB_ERR_ARG, "pb_compose_delta: NULL argument");
   Part p[2] = { { t, sizeof(double) * 3 * c->B, 0 }, { q, sizeof(double) * 4 * c->B, 0 } };
@@ -906,15 +881,14 @@ static int get_state_impl(pb_ctx *c, const double *st, int first, int count, dou
 extern "C" int pb_get_head(pb_ctx *c, int first, int count, double *vec_out, double *quat_out, double *cov_out,
                            double *ll_out, int mem)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   return get_state_impl(c, c->st, first, count, vec_out, quat_out, cov_out, ll_out, mem);
 }
 
 // the same read of a posterior that lives in a checkpoint slot (the head is not touched)
 extern "C" int pb_get_slot(pb_ctx *c, int slot, int first, int count, double *vec_out, double *quat_out, double *cov_out, double *ll_out, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (slot < 0 || slot >= c->nhist) return fail(c, PB_ERR_STATE, "pb_get_slot: checkpoint slot %d of %d", slot, c->nhist);
   return get_state_impl(c, c->hist + (size_t) slot * c->state_doubles, first, count, vec_out, quat_out, cov_out, ll_out, mem);
 }
@@ -993,8 +967,7 @@ static __global__ __launch_bounds__(256) void k_state_checksum(const uint64_t *_
 
 extern "C" int pb_state_checksum(pb_ctx *c, int slot, uint64_t out[2])
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (!out) return PB_ERR_ARG;
   if (slot >= c->nhist) return fail(c, PB_ERR_ARG, "pb_state_checksum: slot %d of %d", slot, c->nhist);
   const double *src = slot < 0 ? c->st : c->hist + (size_t) slot * c->state_doubles;
@@ -1010,8 +983,7 @@ extern "C" int pb_state_checksum(pb_ctx *c, int slot, uint64_t out[2])
 
 extern "C" int pb_summary(pb_ctx *c, double out[4])
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (!out) return PB_ERR_ARG;
   const int nb = nblk(c->B);
   int rc = stage_reserve(c, sizeof(double) * 4 * (size_t) nb);
@@ -1050,7 +1022,7 @@ static __global__ __launch_bounds__(256) void k_mask_count(const uint8_t *__rest
 
 extern "C" int pb_mask_count(pb_ctx *c, const uint8_t *mask_dev, int *count_out)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!mask_dev || !count_out) return fail(c, PB_ERR_ARG, "pb_mask_count: NULL argument");
   int rc = stage_reserve(c, sizeof(unsigned));
   if (rc) return rc;
@@ -1092,8 +1064,7 @@ static int launch_nll(pb_ctx *c, int m, const int *idx, const double *tv, const 
 extern "C" int pb_window_nll(pb_ctx *c, int m, const int *idx, const double *truth_vec, const double *truth_quat,
                              double *out3, double *err_out, int mem)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (m < 1 || m > 9 || !idx || !truth_vec || !truth_quat || !out3) return fail(c, PB_ERR_ARG, "pb_window_nll: bad argument");
   for (int i = 0; i < m; i++) {
     if (idx[i] < 0 || idx[i] >= c->ns) return fail(c, PB_ERR_ARG, "pb_window_nll: index %d out of range", idx[i]);
@@ -1129,7 +1100,7 @@ extern "C" int pb_window_nll(pb_ctx *c, int m, const int *idx, const double *tru
 
 extern "C" int pb_legodo_init(pb_ctx *c, double lt, double ht, int64_t low_delay, int64_t high_delay, int filter_contact_events)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!(ht >= lt) || low_delay < 0 || high_delay < 0) return fail(c, PB_ERR_ARG, "pb_legodo_init: need high >= low threshold, delays >= 0");
   if (low_delay > 2000000000LL || high_delay > 2000000000LL) return fail(c, PB_ERR_ARG, "pb_legodo_init: delays must be below 2e9 us");
   if (!c->legd) HIPCHK(c, hipMalloc((void **) &c->legd, sizeof(double) * (NLD + NLD_WC) * c->stride));
@@ -1151,7 +1122,7 @@ extern "C" int pb_legodo_init(pb_ctx *c, double lt, double ht, int64_t low_delay
 extern "C" int pb_legodo_set_contact_mode(pb_ctx *c, int standing, double total_force, double standing_schmitt_level,
                                           int use_controller_input)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_contact_mode before pb_legodo_init");
   c->leg_par.standing = standing ? 1 : 0;
   c->leg_par.total_force = (float) total_force;                        // float members (FootContact.h:24-28)
@@ -1162,7 +1133,7 @@ extern "C" int pb_legodo_set_contact_mode(pb_ctx *c, int standing, double total_
 
 extern "C" int pb_legodo_set_message_times(pb_ctx *c, const int64_t *utimes, const uint8_t *valid, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_message_times before pb_legodo_init");
   if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_legodo_set_message_times: mem must be PB_HOST or PB_DEVICE");
   c->leg_ut_on = c->leg_valid_on = false;
@@ -1188,28 +1159,9 @@ extern "C" int pb_legodo_set_message_times(pb_ctx *c, const int64_t *utimes, con
   if (utimes || valid) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's arrays are free again
   return PB_OK;
 }
-// The one-shot per-filter times / validity belong to the NEXT odometry or pair call, whatever becomes of it: every such entry point
-// takes them FIRST, before it validates anything, so that a call that fails early cannot leave them behind for an unrelated later
-// call.
-struct LegMsgTimes {
-  const int64_t *utimes = nullptr;
-  const uint8_t *valid = nullptr;
-};
-static LegMsgTimes leg_take_message_times(pb_ctx *c)
-{
-  LegMsgTimes t;
-  if (c == nullptr) return t;
-  if (c->leg_ut_on) t.utimes = c->leg_ut_ext ? c->leg_ut_ext : c->leg_ut;
-  if (c->leg_valid_on) t.valid = c->leg_valid_ext ? c->leg_valid_ext : c->leg_valid;
-  c->leg_ut_on = c->leg_valid_on = false;
-  c->leg_ut_ext = nullptr;
-  c->leg_valid_ext = nullptr;
-  return t;
-}
-
 extern "C" int pb_legodo_set_measurement_mode(pb_ctx *c, int mode, double r_xyz, double r_vang, double r_vang_uncertain)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_measurement_mode before pb_legodo_init");
   if (mode < 0 || mode > 2) return fail(c, PB_ERR_ARG, "pb_legodo_set_measurement_mode: mode 0 (lin_rate), 1 (lin_rot_rate) or 2 (pos_and_lin_rate)");
   c->leg_meas = LegMeasPar{};
@@ -1223,7 +1175,7 @@ extern "C" int pb_legodo_set_measurement_mode(pb_ctx *c, int mode, double r_xyz,
 
 extern "C" int pb_legodo_set_zero_initial_velocity(pb_ctx *c, int ticks)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_zero_initial_velocity before pb_legodo_init");
   if (ticks > 65535) return fail(c, PB_ERR_ARG, "pb_legodo_set_zero_initial_velocity: at most 65535 ticks (16-bit per-robot counter)");
   k_legodo_reset<<<nblk(c->B), 64, 0, c->stream>>>(c->legd, c->legi, c->stride, c->B, ticks < 0 ? 0 : ticks);
@@ -1233,7 +1185,7 @@ extern "C" int pb_legodo_set_zero_initial_velocity(pb_ctx *c, int ticks)
 
 extern "C" int pb_legodo_set_control_contacts(pb_ctx *c, const int32_t *n_contacts, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_control_contacts before pb_legodo_init");
   if (!n_contacts) return fail(c, PB_ERR_ARG, "pb_legodo_set_control_contacts: NULL input");
   if (mem == PB_HOST_BROADCAST) {
@@ -1255,7 +1207,7 @@ extern "C" int pb_legodo_set_control_contacts(pb_ctx *c, const int32_t *n_contac
 extern "C" int pb_legodo_set_chain(pb_ctx *c, int n_left, int n_right, const int *joint_type, const int *joint_row,
                                    const double *origin_xyz_rpy, const double *axis, const float *adjustment_gain)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (n_left < 1 || n_right < 1 || n_left > LEG_MAXJ || n_right > LEG_MAXJ)
     return fail(c, PB_ERR_ARG, "pb_legodo_set_chain: 1..%d joints per leg", LEG_MAXJ);
   if (!joint_type || !joint_row || !origin_xyz_rpy || !axis) return fail(c, PB_ERR_ARG, "pb_legodo_set_chain: NULL input");
@@ -1286,7 +1238,7 @@ extern "C" int pb_legodo_set_chain(pb_ctx *c, int n_left, int n_right, const int
 // ---- joint-position filters in front of the kinematics (leg_estimate.cpp:411-428) ----------------------------------
 extern "C" int pb_joint_filter_init(pb_ctx *c, int mode, double process_noise_pos, double process_noise_vel, double observation_noise)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (mode != JF_LOWPASS && mode != JF_KALMAN) return fail(c, PB_ERR_ARG, "pb_joint_filter_init: mode must be 1 (lowpass) or 2 (kalman)");
   if (!c->leg_chain) return fail(c, PB_ERR_STATE, "pb_joint_filter_init before pb_legodo_set_chain");
   JfPar par;
@@ -1328,7 +1280,7 @@ extern "C" int pb_joint_filter_init(pb_ctx *c, int mode, double process_noise_po
 extern "C" int pb_joint_filter(pb_ctx *c, int64_t utime, int n_rows, const float *joint_position, const float *joint_velocity,
                                const float *joint_effort, int mem, float *joint_position_out)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->jf_ready) return fail(c, PB_ERR_STATE, "pb_joint_filter before pb_joint_filter_init (or the chain changed since)");
   if (!joint_position || !joint_position_out) return fail(c, PB_ERR_ARG, "pb_joint_filter: NULL input");
   if (n_rows < c->leg_chain_rows) return fail(c, PB_ERR_ARG, "pb_joint_filter: the chain reads joint row %d, the block has %d rows", c->leg_chain_rows - 1, n_rows);
@@ -1448,23 +1400,28 @@ static int leg_in_joints(pb_ctx *c, const char *who, int n_rows, const float *jp
   return PB_OK;
 }
 
-static int legodo_launch(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const double *imu_block, int imu_mem, int64_t utime, int zero_delta, double r_vxyz,
-                         double r_vxyz_uncertain, double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out,
-                         double *pos_out = nullptr, uint8_t *pos_ok_out = nullptr)
+// the foot-pose inputs of one message (LegIn kind 0): one robot's poses for every filter travel as kernel arguments, no device block
+static int leg_in_feet(pb_ctx *c, const double *feet, const double *forces, int mem, LegIn &in)
 {
-  LegAhead ah;
-  if (imu_block) {
-    ah.on = 1;
-    if (imu_mem == PB_HOST_BROADCAST) {
-      memcpy(ah.v, imu_block, sizeof(ah.v));
-      ah.bcast = 1;
-    } else {
-      Part pi[1] = { { imu_block, sizeof(double) * 7 * c->B, 0 } };
-      int rc = stage_in(c, imu_mem, pi, 1);
-      if (rc) return rc;
-      ah.imu = (const double *) pi[0].dev;
-    }
+  if (mem == PB_HOST_BROADCAST) {
+    memcpy(in.v, feet, sizeof(double) * 14);
+    in.v[14] = forces[0];
+    in.v[15] = forces[1];
+    in.bcast = 1;
+    return PB_OK;
   }
+  Part p[2] = { { feet, sizeof(double) * 14 * c->B, 0 }, { forces, sizeof(double) * 2 * c->B, 0 } };
+  int rc = stage_in(c, mem, p, 2);
+  if (rc) return rc;
+  in.feet = (const double *) p[0].dev;
+  in.forces = (const double *) p[1].dev;
+  return PB_OK;
+}
+
+// what the context adds to the inputs of an odometry launch: the controller's contact counts, the call's message times, and the
+// measurement mode with the two noises of this call
+static LegMeasPar leg_complete(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, double r_vxyz, double r_vxyz_uncertain)
+{
   if (c->leg_nc_dev) in.ncontacts = c->leg_nc;
   in.nc[0] = c->leg_nc_h[0];
   in.nc[1] = c->leg_nc_h[1];
@@ -1473,11 +1430,15 @@ static int legodo_launch(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const doub
   LegMeasPar mp = c->leg_meas;
   mp.r_v2 = r_vxyz * r_vxyz;                            // bot_sq (rbis_legodo_common.cpp:40-43)
   mp.r_v2_uncertain = r_vxyz_uncertain * r_vxyz_uncertain;
-  // the world constraint (the transition foot's world position) is tracked from the first call that asks for the position
-  if (pos_out != nullptr) c->leg_par.world_constraint = 1;
-  // per-filter joint blocks: two waves per 64 robots, one leg's forward kinematics each
+  return mp;
+}
+
+// the odometry kernel.  split: two waves per 64 robots, one leg's forward kinematics each (per-filter joint blocks)
+static int legodo_kernel(pb_ctx *c, bool split, const LegIn &in, const LegAhead &ah, int64_t utime, int zero_delta, const LegMeasPar &mp,
+                         double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out, double *pos_out, uint8_t *pos_ok_out)
+{
 #define LEGODO_ARGS c->st, c->legd, c->legi, c->stride, c->B, utime, c->leg_par, in, c->leg_chain, ah, zero_delta, mp, delta_out, status_out, lo_out, mask_out, pos_out, pos_ok_out, c->k
-  if (in.kind == 1) {
+  if (split) {
     if (c->ns == 15) k_legodo<15, true><<<nblk(c->B), 128, 0, c->stream>>>(LEGODO_ARGS);
     else k_legodo<21, true><<<nblk(c->B), 128, 0, c->stream>>>(LEGODO_ARGS);
   } else {
@@ -1489,30 +1450,33 @@ static int legodo_launch(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const doub
   return PB_OK;
 }
 
-static int legodo_update_impl(pb_ctx *c, const double *imu_block, int imu_mem, bool ahead, int64_t utime, const double *feet,
+static int legodo_launch(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const double *imu_block, int imu_mem, int64_t utime, int zero_delta, double r_vxyz,
+                         double r_vxyz_uncertain, double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out,
+                         double *pos_out = nullptr, uint8_t *pos_ok_out = nullptr)
+{
+  LegAhead ah;
+  if (imu_block) {
+    StepBcast bc;
+    Part p[1];
+    if (int rc = imu_in(c, imu_block, imu_mem, bc, p)) return rc;
+    ah = leg_ahead(bc, (const double *) p[0].dev);
+  }
+  const LegMeasPar mp = leg_complete(c, in, mt, r_vxyz, r_vxyz_uncertain);
+  // the world constraint (the transition foot's world position) is tracked from the first call that asks for the position
+  if (pos_out != nullptr) c->leg_par.world_constraint = 1;
+  return legodo_kernel(c, in.kind == 1, in, ah, utime, zero_delta, mp, delta_out, status_out, lo_out, mask_out, pos_out, pos_ok_out);
+}
+
+static int legodo_update_impl(pb_ctx *c, const LegMsgTimes &mt, const double *imu_block, int imu_mem, bool ahead, int64_t utime, const double *feet,
                               const double *forces, int mem, int zero_delta, double r_vxyz, double r_vxyz_uncertain,
                               double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out)
 {
-  const LegMsgTimes mt = leg_take_message_times(c);
-  ENTER(c);
-  NEED_STATE(c);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_update before pb_legodo_init");
   if (!feet || !forces || (ahead && !imu_block)) return fail(c, PB_ERR_ARG, "pb_legodo_update: NULL input");
   if (ahead && imu_mem == PB_HOST && mem == PB_HOST)
     return fail(c, PB_ERR_ARG, "pb_legodo_update_after_predict: the IMU block and the foot blocks cannot both be PB_HOST");
   LegIn in;
-  if (mem == PB_HOST_BROADCAST) {  // one robot's foot poses for every filter: kernel arguments, no device block
-    memcpy(in.v, feet, sizeof(double) * 14);
-    in.v[14] = forces[0];
-    in.v[15] = forces[1];
-    in.bcast = 1;
-  } else {
-    Part p[2] = { { feet, sizeof(double) * 14 * c->B, 0 }, { forces, sizeof(double) * 2 * c->B, 0 } };
-    int rc = stage_in(c, mem, p, 2);
-    if (rc) return rc;
-    in.feet = (const double *) p[0].dev;
-    in.forces = (const double *) p[1].dev;
-  }
+  if (int rc = leg_in_feet(c, feet, forces, mem, in)) return rc;
   return legodo_launch(c, in, mt, ahead ? imu_block : nullptr, imu_mem, utime, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out, status_out,
                        lo_out, mask_out);
 }
@@ -1521,7 +1485,8 @@ extern "C" int pb_legodo_update(pb_ctx *c, int64_t utime, const double *feet, co
                                 double r_vxyz, double r_vxyz_uncertain, double *delta_out, double *status_out, double *lo_out,
                                 uint8_t *mask_out)
 {
-  return legodo_update_impl(c, nullptr, PB_DEVICE, false, utime, feet, forces, mem, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out,
+  CALL(c, LEG_TIMES | NEEDS_STATE);
+  return legodo_update_impl(c, call.times, nullptr, PB_DEVICE, false, utime, feet, forces, mem, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out,
                             status_out, lo_out, mask_out);
 }
 
@@ -1529,7 +1494,8 @@ extern "C" int pb_legodo_update_after_predict(pb_ctx *c, const double *imu_block
                                               const double *forces, int mem, int zero_delta, double r_vxyz, double r_vxyz_uncertain,
                                               double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out)
 {
-  return legodo_update_impl(c, imu_block, imu_mem, true, utime, feet, forces, mem, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out,
+  CALL(c, LEG_TIMES | NEEDS_STATE);
+  return legodo_update_impl(c, call.times, imu_block, imu_mem, true, utime, feet, forces, mem, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out,
                             status_out, lo_out, mask_out);
 }
 
@@ -1538,9 +1504,7 @@ extern "C" int pb_legodo_update_joints(pb_ctx *c, const double *imu_block, int i
                                        int zero_delta, double r_vxyz, double r_vxyz_uncertain, double *delta_out, double *status_out,
                                        double *lo_out, uint8_t *mask_out, double *position_out, uint8_t *position_status_out)
 {
-  const LegMsgTimes mt = leg_take_message_times(c);
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, LEG_TIMES | NEEDS_STATE);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_update_joints before pb_legodo_init");
   if (!forces) return fail(c, PB_ERR_ARG, "pb_legodo_update_joints: NULL input");
   if (imu_block && imu_mem == PB_HOST && mem == PB_HOST)
@@ -1548,7 +1512,7 @@ extern "C" int pb_legodo_update_joints(pb_ctx *c, const double *imu_block, int i
   LegIn in;
   int rc = leg_in_joints(c, "pb_legodo_update_joints", n_rows, joint_position, joint_effort, forces, mem, in);
   if (rc) return rc;
-  return legodo_launch(c, in, mt, imu_block, imu_mem, utime, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out, status_out, lo_out, mask_out,
+  return legodo_launch(c, in, call.times, imu_block, imu_mem, utime, zero_delta, r_vxyz, r_vxyz_uncertain, delta_out, status_out, lo_out, mask_out,
                        position_out, position_status_out);
 }
 
@@ -1559,24 +1523,10 @@ static int step_leg_impl(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const doub
                          double r_vxyz_uncertain, double *lo_out, uint8_t *mask_out)
 {
   StepBcast bc;
-  const double *d_imu = nullptr;
-  if (imu_mem == PB_HOST_BROADCAST) {
-    memcpy(bc.imu, imu_block, sizeof(bc.imu));
-    bc.on = 1;
-  } else {
-    Part pi[1] = { { imu_block, sizeof(double) * 7 * c->B, 0 } };
-    int rc = stage_in(c, imu_mem, pi, 1);
-    if (rc) return rc;
-    d_imu = (const double *) pi[0].dev;
-  }
-  if (c->leg_nc_dev) in.ncontacts = c->leg_nc;
-  in.nc[0] = c->leg_nc_h[0];
-  in.nc[1] = c->leg_nc_h[1];
-  in.utimes = mt.utimes;
-  in.valid = mt.valid;
-  LegMeasPar mp = c->leg_meas;
-  mp.r_v2 = r_vxyz * r_vxyz;                            // bot_sq (rbis_legodo_common.cpp:40-43)
-  mp.r_v2_uncertain = r_vxyz_uncertain * r_vxyz_uncertain;
+  Part pi[1];
+  if (int rc = imu_in(c, imu_block, imu_mem, bc, pi)) return rc;
+  const double *d_imu = (const double *) pi[0].dev;
+  const LegMeasPar mp = leg_complete(c, in, mt, r_vxyz, r_vxyz_uncertain);
   if (mp.mode == 2) c->leg_par.world_constraint = 1;    // the measured position IS leg_estimate's world constraint, tracked from here on
   int rc = pbk_step_leg(c, d_imu, &bc, q, in, utime, mp, lo_out, mask_out);
   if (rc >= 0) return rc;
@@ -1587,18 +1537,9 @@ static int step_leg_impl(pb_ctx *c, LegIn &in, const LegMsgTimes &mt, const doub
     lo_out = c->leg_lo;
     mask_out = (uint8_t *) (c->leg_lo + (size_t) rows * c->B);
   }
-  LegAhead ah;
-  ah.on = 1;
-  ah.bcast = bc.on & 1;
-  memcpy(ah.v, bc.imu, sizeof(ah.v));
-  ah.imu = d_imu;
-  if (c->ns == 15)
-    k_legodo<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->legd, c->legi, c->stride, c->B, utime, c->leg_par, in, c->leg_chain, ah, 0, mp, nullptr,
-                                                   nullptr, lo_out, mask_out, nullptr, nullptr, c->k);
-  else
-    k_legodo<21><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->legd, c->legi, c->stride, c->B, utime, c->leg_par, in, c->leg_chain, ah, 0, mp, nullptr,
-                                                   nullptr, lo_out, mask_out, nullptr, nullptr, c->k);
-  LAUNCHCHK(c);
+  // (one wave per 64 robots here, also for per-filter joint blocks)
+  rc = legodo_kernel(c, false, in, leg_ahead(bc, d_imu), utime, 0, mp, nullptr, nullptr, lo_out, mask_out, nullptr, nullptr);
+  if (rc) return rc;
   if (mp.mode == 0) return pbk_step(c, true, d_imu, lo_out, mask_out, q, &bc);
   rc = pbk_step(c, false, d_imu, nullptr, nullptr, q, &bc);
   if (rc) return rc;
@@ -1617,11 +1558,7 @@ extern "C" int pb_step_legodo_joints(pb_ctx *c, const double *imu_block, int imu
                                      const float *joint_position, const float *joint_effort, const float *forces, int mem,
                                      double r_vxyz, double r_vxyz_uncertain, double *lo_block_out, uint8_t *mask_out)
 {
-  ImuIdleTake idle(c);
-  const LegMsgTimes mt = leg_take_message_times(c);
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_step_legodo_joints")) return rc;
-  NEED_STATE(c);
+  CALL(c, IMU_STEP | LEG_TIMES | PRED_REFUSE | NEEDS_STATE);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_step_legodo_joints before pb_legodo_init");
   if (!imu_block || !q || !forces || (lo_block_out && !mask_out)) return fail(c, PB_ERR_ARG, "pb_step_legodo_joints: NULL input");
   if (imu_mem == PB_HOST && mem == PB_HOST)
@@ -1629,41 +1566,26 @@ extern "C" int pb_step_legodo_joints(pb_ctx *c, const double *imu_block, int imu
   LegIn in;
   int rc = leg_in_joints(c, "pb_step_legodo_joints", n_rows, joint_position, joint_effort, forces, mem, in);
   if (rc) return rc;
-  return step_leg_impl(c, in, mt, imu_block, imu_mem, q, utime, r_vxyz, r_vxyz_uncertain, lo_block_out, mask_out);
+  return step_leg_impl(c, in, call.times, imu_block, imu_mem, q, utime, r_vxyz, r_vxyz_uncertain, lo_block_out, mask_out);
 }
 
 extern "C" int pb_step_legodo_feet(pb_ctx *c, const double *imu_block, int imu_mem, const double q[4], int64_t utime, const double *feet,
                                    const double *forces, int mem, double r_vxyz, double r_vxyz_uncertain, double *lo_block_out,
                                    uint8_t *mask_out)
 {
-  ImuIdleTake idle(c);
-  const LegMsgTimes mt = leg_take_message_times(c);
-  ENTER(c);
-  if (int rc = refuse_pred(c, "pb_step_legodo_feet")) return rc;
-  NEED_STATE(c);
+  CALL(c, IMU_STEP | LEG_TIMES | PRED_REFUSE | NEEDS_STATE);
   if (!c->legd) return fail(c, PB_ERR_STATE, "pb_step_legodo_feet before pb_legodo_init");
   if (!imu_block || !q || !feet || !forces || (lo_block_out && !mask_out)) return fail(c, PB_ERR_ARG, "pb_step_legodo_feet: NULL input");
   if (imu_mem == PB_HOST && mem == PB_HOST)
     return fail(c, PB_ERR_ARG, "pb_step_legodo_feet: the IMU block and the foot blocks cannot both be PB_HOST");
   LegIn in;
-  if (mem == PB_HOST_BROADCAST) {
-    memcpy(in.v, feet, sizeof(double) * 14);
-    in.v[14] = forces[0];
-    in.v[15] = forces[1];
-    in.bcast = 1;
-  } else {
-    Part p[2] = { { feet, sizeof(double) * 14 * c->B, 0 }, { forces, sizeof(double) * 2 * c->B, 0 } };
-    int rc = stage_in(c, mem, p, 2);
-    if (rc) return rc;
-    in.feet = (const double *) p[0].dev;
-    in.forces = (const double *) p[1].dev;
-  }
-  return step_leg_impl(c, in, mt, imu_block, imu_mem, q, utime, r_vxyz, r_vxyz_uncertain, lo_block_out, mask_out);
+  if (int rc = leg_in_feet(c, feet, forces, mem, in)) return rc;
+  return step_leg_impl(c, in, call.times, imu_block, imu_mem, q, utime, r_vxyz, r_vxyz_uncertain, lo_block_out, mask_out);
 }
 
 extern "C" int pb_legodo_fk(pb_ctx *c, int n_rows, const float *joint_position, const float *joint_effort, int mem, double *feet_out)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!feet_out) return fail(c, PB_ERR_ARG, "pb_legodo_fk: NULL output");
   LegIn in;
   int rc = leg_in_joints(c, "pb_legodo_fk", n_rows, joint_position, joint_effort, nullptr, mem, in);
@@ -1673,21 +1595,32 @@ extern "C" int pb_legodo_fk(pb_ctx *c, int n_rows, const float *joint_position, 
   return PB_OK;
 }
 
-extern "C" int pb_legodo_get(pb_ctx *c, int filter, double odom_to_body[7], int64_t info[4])
+// Small read-back of one filter's handler state: `launch(dp, di)` leaves up to 16 doubles and 4 info words in the staging area
+template <class Launch>
+static int get_small(pb_ctx *c, double *d_out, int n_d, int64_t info[4], Launch launch)
 {
-  ENTER(c);
-  if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_get before pb_legodo_init");
-  if (filter < 0 || filter >= c->B || !odom_to_body || !info) return fail(c, PB_ERR_ARG, "pb_legodo_get: bad argument");
   int rc = stage_reserve(c, 256);
   if (rc) return rc;
   double *dp = (double *) c->stage;
-  int64_t *di = (int64_t *) (dp + 8);
-  k_legodo_get<<<1, 1, 0, c->stream>>>(c->legd, c->legi, c->stride, filter, dp, di);
-  LAUNCHCHK(c);
-  HIPCHK(c, hipMemcpyAsync(odom_to_body, dp, sizeof(double) * 7, hipMemcpyDeviceToHost, c->stream));
+  int64_t *di = (int64_t *) (dp + 16);
+  rc = launch(dp, di);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(d_out, dp, sizeof(double) * n_d, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipMemcpyAsync(info, di, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return PB_OK;
+}
+
+extern "C" int pb_legodo_get(pb_ctx *c, int filter, double odom_to_body[7], int64_t info[4])
+{
+  CALL(c, 0);
+  if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_get before pb_legodo_init");
+  if (filter < 0 || filter >= c->B || !odom_to_body || !info) return fail(c, PB_ERR_ARG, "pb_legodo_get: bad argument");
+  return get_small(c, odom_to_body, 7, info, [&](double *dp, int64_t *di) -> int {
+    k_legodo_get<<<1, 1, 0, c->stream>>>(c->legd, c->legi, c->stride, filter, dp, di);
+    LAUNCHCHK(c);
+    return PB_OK;
+  });
 }
 
 // ---- yaw lock (rbis_yawlock.hpp, pb_yawlock.hip) ----------------------------------------------------------------------------
@@ -1717,48 +1650,44 @@ extern "C" int pb_yawlock_init(pb_ctx *c, int mode, int correction_period, int y
   return pbk_yawlock_reset(c);
 }
 
-extern "C" int pb_yawlock_set_standing(pb_ctx *c, const uint8_t *standing, int mem)
+// What a handler keeps per filter between messages (pb_yawlock_set_standing / _set_gyro): [B] values in a device array of the
+// context's own, allocated once -- or ONE value for every filter (PB_HOST_BROADCAST), which the caller has stored already.
+template <class T>
+static int keep_per_filter(pb_ctx *c, const char *who, T *&dev, bool &dev_on, const T *src, int mem)
 {
-  ENTER(c);
-  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_standing before pb_yawlock_init");
-  if (!standing) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: NULL input");
   if (mem == PB_HOST_BROADCAST) {
-    c->yaw_standing_all = standing[0] != 0;
-    c->yaw_standing_dev = false;
+    dev_on = false;
     return PB_OK;
   }
-  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: bad mem");
-  if (!c->yaw_standing) HIPCHK(c, hipMalloc((void **) &c->yaw_standing, (size_t) c->stride));
-  HIPCHK(c, hipMemcpyAsync(c->yaw_standing, standing, (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "%s: bad mem", who);
+  if (!dev) HIPCHK(c, hipMalloc((void **) &dev, sizeof(T) * (size_t) c->stride));
+  HIPCHK(c, hipMemcpyAsync(dev, src, sizeof(T) * (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
   if (mem == PB_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
-  c->yaw_standing_dev = true;
+  dev_on = true;
   return PB_OK;
+}
+
+extern "C" int pb_yawlock_set_standing(pb_ctx *c, const uint8_t *standing, int mem)
+{
+  CALL(c, 0);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_standing before pb_yawlock_init");
+  if (!standing) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: NULL input");
+  if (mem == PB_HOST_BROADCAST) c->yaw_standing_all = standing[0] != 0;
+  return keep_per_filter(c, "pb_yawlock_set_standing", c->yaw_standing, c->yaw_standing_dev, standing, mem);
 }
 
 extern "C" int pb_yawlock_set_gyro(pb_ctx *c, const double *body_gyro_z, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_gyro before pb_yawlock_init");
   if (!body_gyro_z) return fail(c, PB_ERR_ARG, "pb_yawlock_set_gyro: NULL input");
-  if (mem == PB_HOST_BROADCAST) {
-    c->yaw_gyro_all = body_gyro_z[0];
-    c->yaw_gyro_dev = false;
-    return PB_OK;
-  }
-  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_yawlock_set_gyro: bad mem");
-  if (!c->yaw_gyro) HIPCHK(c, hipMalloc((void **) &c->yaw_gyro, sizeof(double) * (size_t) c->stride));
-  HIPCHK(c, hipMemcpyAsync(c->yaw_gyro, body_gyro_z, sizeof(double) * (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                           c->stream));
-  if (mem == PB_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));
-  c->yaw_gyro_dev = true;
-  return PB_OK;
+  if (mem == PB_HOST_BROADCAST) c->yaw_gyro_all = body_gyro_z[0];
+  return keep_per_filter(c, "pb_yawlock_set_gyro", c->yaw_gyro, c->yaw_gyro_dev, body_gyro_z, mem);
 }
 
 static int yawlock_impl(pb_ctx *c, const char *who, bool apply, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
                         const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
 {
-  ENTER(c);
-  NEED_STATE(c);
   if (!c->yawd) return fail(c, PB_ERR_STATE, "%s before pb_yawlock_init", who);
   LegIn lin;
   int rc = leg_in_joints(c, who, n_rows, joint_position, nullptr, nullptr, mem, lin);
@@ -1776,36 +1705,28 @@ static int yawlock_impl(pb_ctx *c, const char *who, bool apply, int64_t utime, c
 extern "C" int pb_yawlock_update_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
                                         const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
 {
+  CALL(c, NEEDS_STATE);
   return yawlock_impl(c, "pb_yawlock_update_joints", false, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
 }
 
 extern "C" int pb_step_yawlock_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
                                       const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
 {
-  if (int rc = refuse_pred(c, "pb_step_yawlock_joints")) return rc;
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
   return yawlock_impl(c, "pb_step_yawlock_joints", true, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
 }
 
 extern "C" int pb_yawlock_get(pb_ctx *c, int filter, double poses[14], int64_t info[4])
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_get before pb_yawlock_init");
   if (filter < 0 || filter >= c->B || !poses || !info) return fail(c, PB_ERR_ARG, "pb_yawlock_get: bad argument");
-  int rc = stage_reserve(c, 256);
-  if (rc) return rc;
-  double *dp = (double *) c->stage;
-  int64_t *di = (int64_t *) (dp + 16);
-  rc = pbk_yawlock_get(c, filter, dp, di);
-  if (rc) return rc;
-  HIPCHK(c, hipMemcpyAsync(poses, dp, sizeof(double) * 14, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipMemcpyAsync(info, di, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(c, hipStreamSynchronize(c->stream));
-  return PB_OK;
+  return get_small(c, poses, 14, info, [&](double *dp, int64_t *di) { return pbk_yawlock_get(c, filter, dp, di); });
 }
 
 extern "C" int pb_imu_notch_init(pb_ctx *c, double notch_freq, double fs)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!(notch_freq > 0) || !(fs > 0) || notch_freq * 4 >= fs / 2)
     return fail(c, PB_ERR_ARG, "pb_imu_notch_init: need 0 < 4*notch_freq < fs/2 (got %g, %g)", notch_freq, fs);
   if (!c->notch) HIPCHK(c, hipMalloc((void **) &c->notch, sizeof(double) * 36 * c->stride));
@@ -1833,7 +1754,6 @@ extern "C" int pb_imu_notch_init(pb_ctx *c, double notch_freq, double fs)
 
 static int imu_notch_impl(pb_ctx *c, const char *who, int n_packets, const int32_t *counts, const double *accel_packets, double *accel_out, int mem)
 {
-  ENTER(c);
   if (!c->notch_ready) return fail(c, PB_ERR_STATE, "%s before pb_imu_notch_init", who);
   if (n_packets < 0 || (n_packets > 0 && (!accel_packets || !accel_out))) return fail(c, PB_ERR_ARG, "%s: bad argument", who);
   if (n_packets == 0) return PB_OK;
@@ -1868,18 +1788,20 @@ static int imu_notch_impl(pb_ctx *c, const char *who, int n_packets, const int32
 
 extern "C" int pb_imu_notch(pb_ctx *c, int n_packets, const double *accel_packets, double *accel_out, int mem)
 {
+  CALL(c, 0);
   return imu_notch_impl(c, "pb_imu_notch", n_packets, nullptr, accel_packets, accel_out, mem);
 }
 
 extern "C" int pb_imu_notch_counts(pb_ctx *c, int max_packets, const int32_t *counts, const double *accel_packets, double *accel_out, int mem)
 {
-  if (c && !counts) return fail(c, PB_ERR_ARG, "pb_imu_notch_counts: NULL counts");
+  CALL(c, 0);
+  if (!counts) return fail(c, PB_ERR_ARG, "pb_imu_notch_counts: NULL counts");
   return imu_notch_impl(c, "pb_imu_notch_counts", max_packets, counts, accel_packets, accel_out, mem);
 }
 
 extern "C" int pb_ins_body_reset(pb_ctx *c)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!c->ins_last) {
     HIPCHK(c, hipMalloc((void **) &c->ins_last, sizeof(double) * 6 * (size_t) c->stride));
     HIPCHK(c, hipMalloc((void **) &c->ins_prev_ut, sizeof(int64_t) * (size_t) c->stride));
@@ -1893,7 +1815,7 @@ extern "C" int pb_ins_body_block(pb_ctx *c, const double *gyro, const double *ac
                                  const uint8_t *valid, const double rot_quat[4], const double trans_vec[3], double dt_default, int dt_from_utimes,
                                  int mem, double *imu_block_out, uint8_t *valid_out)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (!gyro || !accel || !rot_quat || !imu_block_out) return fail(c, PB_ERR_ARG, "pb_ins_body_block: NULL argument");
   if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_ins_body_block: mem must be PB_HOST or PB_DEVICE");
   if (!c->ins_last) {
@@ -1932,7 +1854,7 @@ int detach_head(pb_ctx *c, bool keep_contents)
 
 extern "C" int pb_history_reserve(pb_ctx *c, int n_slots)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (n_slots < 0) return fail(c, PB_ERR_ARG, "pb_history_reserve: n_slots < 0");
   int rc = detach_head(c, true);
   if (rc) return rc;
@@ -1954,7 +1876,7 @@ extern "C" int pb_history_reserve(pb_ctx *c, int n_slots)
 
 extern "C" int pb_set_output_slot(pb_ctx *c, int slot)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (slot < -1 || slot >= c->nhist) return fail(c, PB_ERR_STATE, "pb_set_output_slot: checkpoint slot %d of %d", slot, c->nhist);
   c->out_slot = slot;
   return PB_OK;
@@ -1962,7 +1884,7 @@ extern "C" int pb_set_output_slot(pb_ctx *c, int slot)
 
 extern "C" int pb_set_pred_slot(pb_ctx *c, int slot)
 {
-  ENTER(c);
+  CALL(c, 0);
   if (slot == -1) {
     c->pred_slot = -1;
     return PB_OK;
@@ -1982,8 +1904,7 @@ extern "C" int pb_head_slot(const pb_ctx *c)
 
 extern "C" int pb_state_save(pb_ctx *c, int slot)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (slot < 0 || slot >= c->nhist) return fail(c, PB_ERR_STATE, "checkpoint slot %d of %d", slot, c->nhist);
   const size_t n = c->state_doubles;
   double *h = c->hist + (size_t) slot * n;
@@ -1994,8 +1915,7 @@ extern "C" int pb_state_save(pb_ctx *c, int slot)
 
 extern "C" int pb_state_restore(pb_ctx *c, int slot)
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (slot < 0 || slot >= c->nhist) return fail(c, PB_ERR_STATE, "checkpoint slot %d of %d", slot, c->nhist);
   const size_t n = c->state_doubles;
   // always into the context's own array: the slot the head may currently live in stays what it is
@@ -2007,7 +1927,7 @@ extern "C" int pb_state_restore(pb_ctx *c, int slot)
 
 extern "C" int pb_smooth_step(pb_ctx *c, int slot_next_pred, int slot_next, int slot_cur, int slot_out, double dt)
 {
-  ENTER(c);
+  CALL(c, 0);
   const int s[4] = { slot_next_pred, slot_next, slot_cur, slot_out };
   for (int i = 0; i < 4; i++)
     if (s[i] < 0 || s[i] >= c->nhist) return fail(c, PB_ERR_STATE, "pb_smooth_step: checkpoint slot %d of %d", s[i], c->nhist);
@@ -2023,7 +1943,7 @@ extern "C" int pb_smooth_step(pb_ctx *c, int slot_next_pred, int slot_next, int 
 // ---- per-filter selection between posteriors (independent log segments of different lengths) ----
 extern "C" int pb_slot_select(pb_ctx *c, int dst, int src, const uint8_t *mask, int when, int mem)
 {
-  ENTER(c);
+  CALL(c, 0);
   for (int sl : { dst, src })
     if (sl < PB_SLOT_HEAD || sl >= c->nhist) return fail(c, PB_ERR_STATE, "pb_slot_select: checkpoint slot %d of %d", sl, c->nhist);
   if (!mask) return fail(c, PB_ERR_ARG, "pb_slot_select: NULL mask");
@@ -2061,96 +1981,20 @@ extern "C" int pb_smooth_log_slots(int n_steps, int stride)
   return (n_steps + stride - 1) / stride + 2 * stride + 4;
 }
 
-extern "C" int pb_smooth_log(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream, const uint8_t *mask_stream,
-                             const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms)
+// fused: every step of the forward pass and of the recompute pass is ONE launch with the semantics of pb_step_legodo, which in the
+// recompute pass writes the window's predicted slot (pb_set_pred_slot) and its filtered slot together; otherwise the process step and
+// LegOdoCommon's lin_rate update exactly as the per-message path applies them (pb_predict, pb_update_indexed).  Same slots, sink order
+// and head afterwards.  On an error the head goes back to the context's own array (the pre-call head, or the newest posterior once
+// the forward pass is over) and no output / predicted slot is left pending.
+static int smooth_log_impl(pb_ctx *c, const char *who, bool fused, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
+                           const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms)
 {
-  ENTER(c);
-  NEED_STATE(c);
-  if (n_steps < 1 || stride < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_smooth_log: bad argument");
+  if (n_steps < 1 || stride < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "%s: bad argument", who);
   const int K = stride, T = n_steps, M = (T + K - 1) / K, need = pb_smooth_log_slots(T, K);
   if (first_slot < 0 || first_slot + need > c->nhist)
-    return fail(c, PB_ERR_STATE, "pb_smooth_log: needs checkpoint slots [%d, %d), %d are reserved (pb_history_reserve)", first_slot, first_slot + need, c->nhist);
+    return fail(c, PB_ERR_STATE, "%s: needs checkpoint slots [%d, %d), %d are reserved (pb_history_reserve)", who, first_slot, first_slot + need, c->nhist);
   const size_t B = (size_t) c->B, n = c->state_doubles;
   const int CK = first_slot, WP = CK + M, WF = WP + K, PC = WF + K, FIN = PC + 1, SP = FIN + 1;   // checkpoints | window | carry | final | ping-pong
-  auto slot_ptr = [&](int sl) { return c->hist + (size_t) sl * n; };
-  static const int idx_v[3] = { 3, 4, 5 };
-  // one step of the log exactly as the per-message path applies it: the process step, then LegOdoCommon's lin_rate update
-  // (pred_slot / filt_slot < 0: in place)
-  auto step = [&](int j, int pred_slot, int filt_slot) -> int {
-    c->out_slot = pred_slot;
-    int rc = pbk_step(c, false, imu_stream + (size_t) j * 7 * B, nullptr, nullptr, q);
-    if (rc) return rc;
-    c->out_slot = filt_slot;
-    return update_common(c, 3, idx_v, lo_stream + (size_t) j * 6 * B, lo_stream + (size_t) j * 6 * B + 3 * B, PB_R_DIAG, nullptr, false,
-                         mask_stream ? mask_stream + (size_t) j * B : nullptr, PB_DEVICE);
-  };
-  if (elapsed_ms) HIPCHK(c, hipEventRecord(c->ev0, c->stream));
-  int rc = detach_head(c, true);
-  if (rc) return rc;
-  // ---- forward: the filter, a checkpoint in front of every stretch ----
-  for (int j = 0; j < T; j++) {
-    if (j % K == 0) {
-      rc = pb_state_save(c, CK + j / K);
-      if (rc) return rc;
-    }
-    rc = step(j, -1, -1);
-    if (rc) return rc;
-  }
-  rc = pb_state_save(c, FIN);   // the newest posterior: its own smoothed value (and the head again when the pass is over)
-  if (rc) return rc;
-  // ---- backward: stretch by stretch ----
-  int next_sm = FIN, toggle = 0;
-  for (int m = M - 1; m >= 0; m--) {
-    const int s0 = m * K, s1 = std::min(T, s0 + K) - 1;
-    c->st = slot_ptr(CK + m);   // the head lives in the checkpoint: the first process step reads it there and writes into the window
-    c->out_slot = -1;
-    for (int j = s0; j <= s1; j++) {
-      rc = step(j, WP + (j - s0), WF + (j - s0));
-      if (rc) return rc;
-    }
-    for (int j = s1; j >= s0; j--) {
-      if (j == T - 1) continue;   // (the newest step is not smoothed: mav_state_est.cpp:120-131 starts one step behind it)
-      const int np = (j == s1) ? PC : WP + (j + 1 - s0);
-      const int out = SP + toggle;
-      rc = pbk_smooth_step(c, slot_ptr(np), slot_ptr(next_sm), slot_ptr(WF + (j - s0)), slot_ptr(out), dt);
-      if (rc) return rc;
-      if (sink) sink(user, j, out);
-      next_sm = out;
-      toggle ^= 1;
-    }
-    // the earlier stretch's last step needs the process-step posterior of THIS stretch's first step
-    HIPCHK(c, hipMemcpyAsync(slot_ptr(PC), slot_ptr(WP), sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream));
-  }
-  rc = pb_state_restore(c, FIN);
-  if (rc) return rc;
-  if (elapsed_ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
-  }
-  return PB_OK;
-}
-
-// pb_smooth_log with the fused step: every step of the forward pass and of the recompute pass is ONE launch with the semantics of
-// pb_step_legodo; in the recompute pass that launch writes the window's predicted slot (pb_set_pred_slot) and its filtered slot
-// together.  Same slots, sink order and head afterwards as pb_smooth_log.  On an error the head goes back to the context's own
-// array (the pre-call head, or the newest posterior once the forward pass is over) and no output / predicted slot is left pending.
-extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
-                                   const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink,
-                                   void *user, float *elapsed_ms)
-{
-  ENTER(c);
-  c->pred_slot = -1;
-  NEED_STATE(c);
-  int rc = detach_head(c, true);
-  if (rc) return rc;
-  if (n_steps < 1 || stride < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_smooth_log_fused: bad argument");
-  const int K = stride, T = n_steps, M = (T + K - 1) / K, need = pb_smooth_log_slots(T, K);
-  if (first_slot < 0 || first_slot + need > c->nhist)
-    return fail(c, PB_ERR_STATE, "pb_smooth_log_fused: needs checkpoint slots [%d, %d), %d are reserved (pb_history_reserve)", first_slot,
-                first_slot + need, c->nhist);
-  const size_t B = (size_t) c->B, n = c->state_doubles;
-  const int CK = first_slot, WP = CK + M, WF = WP + K, PC = WF + K, FIN = PC + 1, SP = FIN + 1;   // (as pb_smooth_log)
   auto slot_ptr = [&](int sl) { return c->hist + (size_t) sl * n; };
   bool have_fin = false;
   auto bail = [&](int code) -> int {
@@ -2162,32 +2006,43 @@ extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const dou
     }
     return code;
   };
-  // one step of the log as pb_step_legodo applies it (pred_slot / filt_slot < 0: in place)
+  static const int idx_v[3] = { 3, 4, 5 };
+  // one step of the log (pred_slot / filt_slot < 0: in place)
   auto step = [&](int j, int pred_slot, int filt_slot) -> int {
-    c->pred_slot = pred_slot;
+    const double *imu = imu_stream + (size_t) j * 7 * B, *lo = lo_stream + (size_t) j * 6 * B;
+    const uint8_t *mask = mask_stream ? mask_stream + (size_t) j * B : nullptr;
+    if (fused) {
+      c->pred_slot = pred_slot;
+      c->out_slot = filt_slot;
+      const int r = pbk_step(c, true, imu, lo, mask, q);
+      c->pred_slot = -1;
+      return r;
+    }
+    c->out_slot = pred_slot;
+    int rc = pbk_step(c, false, imu, nullptr, nullptr, q);
+    if (rc) return rc;
     c->out_slot = filt_slot;
-    const int r = pbk_step(c, true, imu_stream + (size_t) j * 7 * B, lo_stream + (size_t) j * 6 * B, mask_stream ? mask_stream + (size_t) j * B : nullptr, q);
-    c->pred_slot = -1;
-    return r;
+    return update_common(c, 3, idx_v, lo, lo + 3 * B, PB_R_DIAG, nullptr, false, mask, PB_DEVICE);
   };
-  if (elapsed_ms && hipEventRecord(c->ev0, c->stream) != hipSuccess) return bail(fail(c, PB_ERR_HIP, "pb_smooth_log_fused: hipEventRecord"));
+  int rc = timed_begin(c, elapsed_ms);
+  if (rc || (rc = detach_head(c, true))) return bail(rc);
   // ---- forward: the filter, a checkpoint in front of every stretch ----
   for (int j = 0; j < T; j++) {
     if (j % K == 0 && (rc = pb_state_save(c, CK + j / K))) return bail(rc);
     if ((rc = step(j, -1, -1))) return bail(rc);
   }
-  if ((rc = pb_state_save(c, FIN))) return bail(rc);
+  if ((rc = pb_state_save(c, FIN))) return bail(rc);   // the newest posterior: its own smoothed value (and the head again when the pass is over)
   have_fin = true;
   // ---- backward: stretch by stretch ----
   int next_sm = FIN, toggle = 0;
   for (int m = M - 1; m >= 0; m--) {
     const int s0 = m * K, s1 = std::min(T, s0 + K) - 1;
-    c->st = slot_ptr(CK + m);
+    c->st = slot_ptr(CK + m);   // the head lives in the checkpoint: the first process step reads it there and writes into the window
     c->out_slot = -1;
     for (int j = s0; j <= s1; j++)
       if ((rc = step(j, WP + (j - s0), WF + (j - s0)))) return bail(rc);
     for (int j = s1; j >= s0; j--) {
-      if (j == T - 1) continue;
+      if (j == T - 1) continue;   // (the newest step is not smoothed: mav_state_est.cpp:120-131 starts one step behind it)
       const int np = (j == s1) ? PC : WP + (j + 1 - s0);
       const int out = SP + toggle;
       if ((rc = pbk_smooth_step(c, slot_ptr(np), slot_ptr(next_sm), slot_ptr(WF + (j - s0)), slot_ptr(out), dt))) return bail(rc);
@@ -2195,16 +2050,29 @@ extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const dou
       next_sm = out;
       toggle ^= 1;
     }
+    // the earlier stretch's last step needs the process-step posterior of THIS stretch's first step
     if (hipMemcpyAsync(slot_ptr(PC), slot_ptr(WP), sizeof(double) * n, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-      return bail(fail(c, PB_ERR_HIP, "pb_smooth_log_fused: carry copy"));
+      return bail(fail(c, PB_ERR_HIP, "%s: carry copy", who));
   }
   if ((rc = pb_state_restore(c, FIN))) return bail(rc);
-  if (elapsed_ms) {
-    HIPCHK(c, hipEventRecord(c->ev1, c->stream));
-    HIPCHK(c, hipEventSynchronize(c->ev1));
-    HIPCHK(c, hipEventElapsedTime(elapsed_ms, c->ev0, c->ev1));
-  }
-  return PB_OK;
+  return timed_end(c, elapsed_ms);
+}
+
+extern "C" int pb_smooth_log(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream, const uint8_t *mask_stream,
+                             const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms)
+{
+  CALL(c, PRED_FORGET | NEEDS_STATE);
+  return smooth_log_impl(c, "pb_smooth_log", false, n_steps, stride, imu_stream, lo_stream, mask_stream, q, dt, first_slot, sink, user, elapsed_ms);
+}
+
+extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
+                                   const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink,
+                                   void *user, float *elapsed_ms)
+{
+  CALL(c, PRED_FORGET | NEEDS_STATE);
+  // (ahead of the argument checks: also a call that is refused for its arguments or slots leaves the head in the context's own array)
+  if (int rc = detach_head(c, true)) return rc;
+  return smooth_log_impl(c, "pb_smooth_log_fused", true, n_steps, stride, imu_stream, lo_stream, mask_stream, q, dt, first_slot, sink, user, elapsed_ms);
 }
 
 static int calib_copy_impl(pb_ctx *c, int reps, float *elapsed_ms, uint64_t *checksum)
@@ -2243,14 +2111,13 @@ static int calib_copy_impl(pb_ctx *c, int reps, float *elapsed_ms, uint64_t *che
 
 extern "C" int pb_calib_copy(pb_ctx *c, int reps, float *elapsed_ms)
 {
-  ENTER(c);
+  CALL(c, 0);
   return calib_copy_impl(c, reps, elapsed_ms, nullptr);
 }
 
 extern "C" int pb_calib_copy_checksum(pb_ctx *c, int reps, uint64_t out[2])
 {
-  ENTER(c);
-  NEED_STATE(c);
+  CALL(c, NEEDS_STATE);
   if (!out) return PB_ERR_ARG;
   return calib_copy_impl(c, reps, nullptr, out);
 }

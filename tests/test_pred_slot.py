@@ -229,6 +229,28 @@ def test_pred_slot_errors(oracle):
     est.close()
 
 
+@pytest.mark.parametrize("n", [15, 21])
+def test_pred_slot_is_forgotten_by_the_whole_log_smoother(oracle, n):
+    """pb_smooth_log (the process step and the update as two launches) runs a whole log of steps of its own: a predicted slot that is
+    pending at its entry is forgotten there, as pb_smooth_log_fused forgets it, and the next pb_step_legodo writes no slot."""
+    import torch
+    dev = torch.device("cuda:0")
+    B, T, K = 64, 6, 3
+    w = Workload(B, n_states=n)
+    imu, lo, mask = w.streams(0, T)
+    est, q4 = _fresh(oracle, w, n, B, slots=0)
+    need = est.smooth_log_slots(T, K)
+    est.history_reserve(need + 1)
+    s = need                                             # a slot the smoother does not use
+    before = est.state_checksum(s)
+    est.set_pred_slot(s)
+    est.smooth_log(*(torch.from_numpy(a).to(dev) for a in (imu, lo, mask)), q4, 1e-3, K, first_slot=0)
+    assert est.state_checksum(s) == before
+    est.step_legodo(imu[0], lo[0], mask[0], q4)
+    assert est.state_checksum(s) == before
+    est.close()
+
+
 def test_pred_slot_beyond_the_two_wave_batch_limit(oracle):
     """Above 393 216 15-state filters the step runs one lane per filter (k_step<15>), which has no predicted-slot variant: the predict
     into the slot and the fused step as two launches -- the same contract."""
