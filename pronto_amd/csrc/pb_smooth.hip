@@ -5,15 +5,6 @@
 
 int pbk_smooth_step(pb_ctx *c, const double *np_, const double *ns_, const double *cu, double *out, double dt)
 {
-#ifdef PB_EXPERIMENTS  // attribution builds only (scripts/smooth_attribution.sh): extra dynamic LDS to force fewer workgroups per CU
-  static const size_t pad = [] {
-    const char *e = getenv("PRONTO_SMOOTH_LDS_PAD");
-    const long v = e ? atol(e) : 0;
-    return (size_t) (v < 0 ? 0 : (v > 65536 ? 65536 : v));
-  }();
-#else
-  constexpr size_t pad = 0;
-#endif
   // PRONTO_SMOOTH_PIVOT=1: Eigen's diagonal pivoting in the factorisation of P^- (the reference's .ldlt(); parity with the oracle at
   // 1e-15); default: no pivot search (P^- is SPD; rbis_smooth.hpp)
   static const bool pivot = getenv("PRONTO_SMOOTH_PIVOT") && getenv("PRONTO_SMOOTH_PIVOT")[0] == '1';
@@ -25,9 +16,9 @@ int pbk_smooth_step(pb_ctx *c, const double *np_, const double *ns_, const doubl
   // the second half of round 5, and still the kernel for 21 states)
   static const bool lane15 = getenv("PRONTO_SMOOTH_KERNEL") && !strcmp(getenv("PRONTO_SMOOTH_KERNEL"), "lane");
   if (!c->smooth_attr) {  // more than the default 64 KB of dynamic LDS per workgroup
-    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_lane<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) (SmoothLaneCfg<15>::LDS_BYTES + pad)));
+    HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_lane<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) SmoothLaneCfg<15>::LDS_BYTES));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_lane<21>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) SmoothLaneCfg<21>::LDS_BYTES));
-    const int l15 = (int) (pad + sizeof(double) * SmoothRegCfg<15>::LDS_DOUBLES), l21 = (int) (pad + sizeof(double) * SmoothRegCfg<21>::LDS_DOUBLES);
+    const int l15 = (int) (sizeof(double) * SmoothRegCfg<15>::LDS_DOUBLES), l21 = (int) (sizeof(double) * SmoothRegCfg<21>::LDS_DOUBLES);
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_reg<15, true>), hipFuncAttributeMaxDynamicSharedMemorySize, l15));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_reg<21, true>), hipFuncAttributeMaxDynamicSharedMemorySize, l21));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_reg<15, false>), hipFuncAttributeMaxDynamicSharedMemorySize, l15));
@@ -36,20 +27,19 @@ int pbk_smooth_step(pb_ctx *c, const double *np_, const double *ns_, const doubl
   }
   if (!reg_kernel) {
     const dim3 grid((unsigned) ((c->B + 63) / 64));
-    // (the pad of the attribution builds: past the kernel's own LDS, never touched -- it only keeps a second workgroup off the CU)
     if (c->ns == 15 && !lane15) return pbk_smooth_wide(c, np_, ns_, cu, out, dt);
-    if (c->ns == 15) k_smooth_lane<15><<<grid, SmoothLaneCfg<15>::THREADS, SmoothLaneCfg<15>::LDS_BYTES + pad, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
+    if (c->ns == 15) k_smooth_lane<15><<<grid, SmoothLaneCfg<15>::THREADS, SmoothLaneCfg<15>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
     else k_smooth_lane<21><<<grid, SmoothLaneCfg<21>::THREADS, SmoothLaneCfg<21>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
   } else if (c->ns == 15) {
     using S = SmoothRegCfg<15>;
     const dim3 grid((unsigned) ((c->B + S::F - 1) / S::F));
-    const size_t ldsb = pad + sizeof(double) * S::LDS_DOUBLES;
+    const size_t ldsb = sizeof(double) * S::LDS_DOUBLES;
     if (pivot) k_smooth_reg<15, true><<<grid, S::THREADS, ldsb, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
     else k_smooth_reg<15, false><<<grid, S::THREADS, ldsb, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
   } else {
     using S = SmoothRegCfg<21>;
     const dim3 grid((unsigned) ((c->B + S::F - 1) / S::F));
-    const size_t ldsb = pad + sizeof(double) * S::LDS_DOUBLES;
+    const size_t ldsb = sizeof(double) * S::LDS_DOUBLES;
     if (pivot) k_smooth_reg<21, true><<<grid, S::THREADS, ldsb, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
     else k_smooth_reg<21, false><<<grid, S::THREADS, ldsb, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
   }

@@ -111,9 +111,6 @@ int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const dou
   // the two-wave 15-state mapping (the default up to 393 216 filters) and the four-wave 21-state mapping.  Mode lin_rate with
   // leg_estimate's world constraint switched on needs the stand-alone kernel (mode pos_and_lin_rate tracks it inside the pair kernel).
   if ((c->ns == 15 && !c->coop15) || (c->ns == 21 && !c->quad21) || (c->leg_par.world_constraint && mp.mode != 2)) return -1;
-  // PRONTO_BATCH_LEG21_TWO=1: round 3's two launches for 21 states with per-filter joint blocks (A/B runs)
-  static const bool two_launches21 = getenv("PRONTO_BATCH_LEG21_TWO") && getenv("PRONTO_BATCH_LEG21_TWO")[0] == '1';
-  if (c->ns == 21 && lin.kind == 1 && two_launches21 && mp.mode == 0) return -1;
   const StepBcast bc = bcast ? *bcast : StepBcast();
   LegStepArgs la{ c->legd, c->legi, c->stride, utime, mp.r_v2, mp.r_v2_uncertain, lo_out, mask_out, mp };
   double *out = update_target(c);

@@ -253,7 +253,7 @@ __global__ __launch_bounds__(PB_STEP_BLOCK, 1) void k_step(const double *st, dou
 // path (MavStateEstimator::addUpdate publishes a posterior per message) but what a parameter sweep or a likelihood
 // evaluation over a log segment wants (param_sweep.py:39-52).  Accounting: 104 + 2240/T bytes per filter-step, so the
 // bound moves from HBM to fp64 VALU issue; bench.py reports it separately (never as the headline value).
-// Inputs of step t+1 are prefetched while step t computes (one wave per SIMD: nothing else hides their latency).
+// Each step requests its inputs at its top.
 template <int NS>
 __global__ __launch_bounds__(64, 1) void k_replay_fused(double *__restrict__ st, int B, int T,
                                                         const double *__restrict__ imu, const double *__restrict__ lo,
@@ -279,9 +279,8 @@ __global__ __launch_bounds__(64, 1) void k_replay_fused(double *__restrict__ st,
     qg = ldg(rq, 0u, bo); qa = ldg(rq, B8, bo); qbg = ldg(rq, 2u * B8, bo); qba = ldg(rq, 3u * B8, bo);
   }
   // step-t input blocks are [7][B] / [6][B] / [B] slabs of the streams; 64-bit slab base, 32-bit offsets inside
-  double in[13], nx[13] = { 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0 };
-  bool upd, nupd = false;
-  (void) nx; (void) nupd;  // only used with PB_REPLAY_PREFETCH
+  double in[13];
+  bool upd;
   auto fetch = [&](int t, double (&dst)[13], bool &u) {
     const rsrc_t ri = mkbuf(imu + (size_t) t * 7 * B, 7u * B8);
     const rsrc_t rl = mkbuf(lo + (size_t) t * 6 * B, 6u * B8);
@@ -293,11 +292,7 @@ __global__ __launch_bounds__(64, 1) void k_replay_fused(double *__restrict__ st,
   };
   fetch(0, in, upd);
   for (int t = 0; t < T; t++) {
-#ifdef PB_REPLAY_PREFETCH
-    if (t + 1 < T) fetch(t + 1, nx, nupd);
-#else
     if (t > 0) fetch(t, in, upd);
-#endif
     const double gyro[3] = { in[0], in[1], in[2] }, accel[3] = { in[3], in[4], in[5] };
     imu_process_step<NS>(x, q, P, gyro, accel, in[6], qg, qa, qbg, qba, k);
     double resid[3], S[6];
@@ -308,11 +303,6 @@ __global__ __launch_bounds__(64, 1) void k_replay_fused(double *__restrict__ st,
 #pragma unroll
       for (int j = 0; j <= i; j++) S[pk(i, j)] = P[pk(3 + i, 3 + j)] + (i == j ? (upd ? in[10 + i] : 1.0) : 0.0);
     measurement_update<NS, 3>(x, q, P, ll, resid, S, IdxVel{}, k, NoSink(), upd);
-#ifdef PB_REPLAY_PREFETCH
-#pragma unroll
-    for (int i = 0; i < 13; i++) in[i] = nx[i];
-    upd = nupd;
-#endif
   }
 #pragma unroll
   for (int i = 0; i < L::NP; i++) io.st(L::OFF_P + i, P[i]);

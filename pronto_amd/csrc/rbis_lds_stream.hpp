@@ -1,5 +1,5 @@
 // rbis_lds_stream.hpp -- LDS reads as an explicit, software-pipelined stream of ds_read_b64 (round 5): used by the smoother kernels
-// (rbis_smooth_wide.hpp, rbis_smooth_lane.hpp).  Device code only.
+// (rbis_smooth_wide.hpp).  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>

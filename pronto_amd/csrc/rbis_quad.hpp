@@ -140,12 +140,10 @@ PB_HD void quad_role_cc(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs 
   // 40.6 -> 38.6 us on one box, both libraries in one run; pair kernels 1-4 us)
   // (PIN = false: the time-fused replay kernels, whose state lives in registers incl. AGPRs from step to step -- the pin wants
   // VGPRs: write-through replay 34.4 -> 39.0 us per step with it)
-#ifndef PB_NO_PIN_CC   // (A/B builds)
   if constexpr (PIN) {
 #pragma unroll
     for (int i = 0; i < 45; i++) pb_pin(Pc[i]);
   }
-#endif
   sync();  // A: H and the propagated velocity are there; every role has consumed the prior x / quat
   double leg_z[3] = { 0.0, 0.0, 0.0 }, leg_r = 1.0, leg_valid = 0.0;
   if constexpr (LEG) {  // (read first: this role sits exactly at 256 registers and the allocation is fragile)

@@ -12,14 +12,7 @@
 // The factorisation and the substitutions are VALU + LDS; the two n x n products run on the matrix pipe
 // (v_mfma_f64_16x16x4_f64: one 16 x 16 tile per 15-state filter, 2 x 2 tiles with k padded to 24 per 21-state filter, step 5): its fp64 rate equals the vector rate on MI355X, the
 // gain is the VALU / LDS work and the row registers it takes away, not arithmetic throughput.
-// Build flags SM_SKIP_* / SM_NO_* / SM_COPY_ONLY / SM_EMPTY compile parts out for scripts/smooth_attribution.sh (timing only).
 #pragma once
-
-#if !defined(PB_EXPERIMENTS) && (defined(SM_EMPTY) || defined(SM_NO_LOAD) || defined(SM_NO_STORE) || defined(SM_COPY_ONLY) || \
-                                 defined(SM_SKIP_QUAT) || defined(SM_SKIP_FACT) || defined(SM_SKIP_SUBST) || defined(SM_SKIP_PROD) || \
-                                 defined(SM_OCC3))
-#error "the SM_* attribution flags compile parts of the smoother OUT (garbage results): they need -DPB_EXPERIMENTS as well"
-#endif
 
 #include <hip/hip_runtime.h>
 
@@ -86,11 +79,7 @@ struct SmoothRegCfg {
   // small per-filter buffer of four RBW-wide slots: pivot row of the current step (entry NS = dummy for the padding
   // lanes), reciprocal pivots, residual, dx
   static constexpr int RBW = (NS + 2) & ~1, RB_INV = RBW, RB_RES = 2 * RBW, RB_DX = 3 * RBW, RB = bank_stride(4 * RBW);
-#ifdef SM_OCC3
-  static constexpr int LDS_DOUBLES = F * RB + U_DOUBLES;
-#else
   static constexpr int LDS_DOUBLES = F * RB + U_DOUBLES + F * D_PER;
-#endif
 };
 
 // 16-byte LDS access: p must be an even number of doubles from the (16-byte aligned) start of LDS
@@ -161,14 +150,6 @@ __device__ __forceinline__ unsigned rowpair_min(unsigned v)
   return x[0] < x[1] ? x[0] : x[1];
 }
 
-// SM_OCC3 (attribution build, garbage results): what a THIRD workgroup per CU would buy with this instruction stream -- the D
-// buffer aliases the gain buffer (LDS per workgroup 77.6 -> 43 KB for 15 states) and the register budget is the 168 of three
-// waves per SIMD (whatever does not fit goes to scratch): an upper bound for the restructuring DESIGN.md 4 describes.
-#ifdef SM_OCC3
-#define PB_SMOOTH_WG_PER_CU 3
-#else
-#define PB_SMOOTH_WG_PER_CU 2
-#endif
 // PIVOT = true: Eigen's diagonal pivoting (the reference calls .ldlt(): same pivot sequence, parity with the oracle at 1e-15).
 // PIVOT = false: NO pivot search -- P^- (with the bias-block fix) is symmetric positive definite, for which the unpivoted
 // factorisation is backward stable and its accuracy, like Cholesky's, is governed by the condition of the diagonally SCALED
@@ -177,7 +158,7 @@ __device__ __forceinline__ unsigned rowpair_min(unsigned v)
 // bookkeeping and the permutation of the right-hand side disappear.  Results differ from the pivoted path by rounding
 // (tests: <= 1e-9 against the oracle; observed 1e-13).
 template <int NS, bool PIVOT = true>
-__global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(const double *__restrict__ next_pred,
+__global__ __launch_bounds__(SM_THREADS, 2) void k_smooth_reg(const double *__restrict__ next_pred,
                                                     const double *__restrict__ next_sm,
                                                     const double *__restrict__ cur, double *__restrict__ out,
                                                     int B, double dt, Consts k)
@@ -185,25 +166,13 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
   using L = Lay<NS>;
   using SL = Slots<NS>;
   using C = SmoothRegCfg<NS>;
-  constexpr int G = C::G, F = C::F, PITCH = C::PITCH, PG = C::PG, MATP = C::MATP;
+  constexpr int G = C::G, F = C::F, PITCH = C::PITCH, PG = C::PG;
   constexpr bool MFMA = (NS <= 16);  // the two n x n products of step 5 on v_mfma_f64_16x16x4 (one 16 x 16 tile per filter)
   constexpr bool MFMA21 = !MFMA;     // 21 states: the same on 2 x 2 tiles of 16 x 16 with k padded to 24 (two filters per wave)
   static_assert(!MFMA || (G == 16 && PG >= 16), "one filter per 16-lane group, rows padded to 16 columns");
   static_assert(NS < 24 && C::U_DOUBLES >= F * PITCH + C::THREADS, "buffer slots");
   extern __shared__ __attribute__((aligned(16))) double lds[];
-#ifdef SM_EMPTY  // workgroup dispatch cost alone: same registers, same LDS request, no work
-  if (B > 0) return;
-#endif
-#ifdef SM_SKEW  // attribution: the second workgroup of every CU in the first dispatch round starts SM_SKEW x 3.4 us late, so that
-                // the two workgroups of a CU are out of phase (one stages while the other computes) instead of in lock-step
-  if (blockIdx.x >= 256 && blockIdx.x < 512)
-    for (int i = 0; i < SM_SKEW; i++) __builtin_amdgcn_s_sleep(127);
-#endif
-#ifdef SM_OCC3
-  double *U = lds + F * C::RB, *DP = U;
-#else
   double *U = lds + F * C::RB, *DP = U + C::U_DOUBLES;  // [small buffers | staging / x / L / gain | D packed]
-#endif
   const int t = threadIdx.x;
   const int f = t / G, r = t % G;        // compute mapping: filter slot f, matrix row r
   const int sf = t % F, sc = t / F;      // staging mapping: filter fastest
@@ -228,11 +197,7 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
 #pragma unroll
     for (int i = 0; i < NST; i++) {
       const int r2 = sc + i * G;
-#ifdef SM_NO_LOAD
-      v[i] = d2_t{ 1.0 + 0.001 * r2 + 1e-6 * threadIdx.x, 0.5 + 0.002 * r2 };
-#else
       v[i] = (r2 < SL::NROW) ? *reinterpret_cast<const d2_t *>(src + srow0 + (long) r2 * 128) : d2_t{ 0.0, 0.0 };
-#endif
     }
   };
   auto commit = [&](const d2_t (&v)[NST]) {
@@ -312,11 +277,7 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
     double qs[4], dchi[3];
 #pragma unroll
     for (int i = 0; i < 4; i++) qs[i] = Uf[L::OFF_QUAT + i];
-#ifdef SM_SKIP_QUAT
-    dchi[0] = qs[1] - qp[1]; dchi[1] = qs[2] - qp[2]; dchi[2] = qs[3] - qp[3];
-#else
     subtract_quats(qs, qp, dchi);  // chi = Log(q^-^-1 q^s)   (rbis.cpp:259-261)
-#endif
     double res = Uf[L::OFF_VEC + rr] - xpr;
     if (rr >= 6 && rr <= 8) res = (rr == 6) ? dchi[0] : (rr == 7 ? dchi[1] : dchi[2]);
     Rf[row ? C::RB_RES + rr : NS] = res;
@@ -324,17 +285,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
   __syncthreads();
   commit(vc);
   __syncthreads();
-#ifdef SM_COPY_ONLY
-  if (b0 + sf < B) {
-#pragma unroll 4
-    for (int r2 = sc; r2 < SL::NROW; r2 += G) {
-      const int c0 = SL::T.comp_of[2 * r2], c1 = SL::T.comp_of[2 * r2 + 1];
-      const d2_t v2 = { U[sf * PITCH + c0] + am[0], c1 >= 0 ? U[sf * PITCH + c1] : 0.0 };
-      *reinterpret_cast<d2_t *>(out + srow0 + (long) r2 * 128) = v2;
-    }
-  }
-  return;
-#endif
   double w[3], v[3], q[4];
 #pragma unroll
   for (int j = 0; j < NS; j++) prow[j] = Uf[poff[j]];
@@ -375,9 +325,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
     int pos = r;                 // current position of this row under Eigen's swaps (tie-break only)
     static_for<NS>([&](auto KK) {
       constexpr int kk = decltype(KK)::value;
-#ifdef SM_SKIP_FACT
-      piv[kk] = kk; if (r == kk) mypos = kk; if constexpr (KEEP_L) lreg[kk] = 0.0; Rf[C::RB_INV + kk] = 1.0; return;
-#endif
       if constexpr (!PIVOT) {
         const bool is_k = row && (r == kk);
         piv[kk] = kk;
@@ -502,9 +449,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
   group_sync();
   static_for<NS>([&](auto KK) {  // forward: z[kk] -= sum_{m<kk} L[kk][m] z[m], row kk read 16 bytes at a time
     constexpr int kk = decltype(KK)::value;
-#ifdef SM_SKIP_SUBST
-    return;
-#endif
     double s = z[kk];
 #pragma unroll
     for (int m = 0; m < kk; m += 2) {
@@ -528,9 +472,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
   group_sync();
   static_for<NS>([&](auto KR) {  // backward: z[kk] -= sum_{m>kk} L[m][kk] z[m]
     constexpr int kk = NS - 1 - decltype(KR)::value;
-#ifdef SM_SKIP_SUBST
-    return;
-#endif
     double s = z[kk];
 #pragma unroll
     for (int m = (kk + 1) & ~1; m < NS; m += 2) {
@@ -594,7 +535,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
     // 15 states on the matrix pipe: F = D G^T, then P^s = P_k + G F, one 16 x 16 x 16 product = four v_mfma_f64_16x16x4 each,
     // for the four filters of this wave (independent chains).  Lane (h, j) supplies D[j][h + 4 s] and G[j][h + 4 s]
     // (s = 0..3: contiguous in mfma_pos order), F's result register s IS the B operand of k-slice s of the second product.
-#ifndef SM_SKIP_PROD
     d4_t gq[4], dq[4];
 #pragma unroll
     for (int ff = 0; ff < 4; ff++) {
@@ -614,9 +554,7 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
     for (int s4 = 0; s4 < 4; s4++)
 #pragma unroll
       for (int ff = 0; ff < 4; ff++) acc[ff] = __builtin_amdgcn_mfma_f64_16x16x4f64(gq[ff][s4], fq[ff][s4], acc[ff], 0, 0, 0);
-#endif
   } else {
-#ifndef SM_SKIP_PROD
     // 21 states on the matrix pipe: 2 x 2 tiles of 16 x 16, k padded to 24 = 6 slices.  F = D G^T (4 tiles x 6 MFMAs), then the
     // lower tiles (0,0), (1,0), (1,1) of G F (3 x 6): F's tile (tk, tj) has row 16 tk + h + 4 v in result register v of lane
     // (h, j) -- the B operand of k-slice (tk, v) -- and the matching A operand G[i][16 tk + h + 4 v] is slice 4 tk + v of the
@@ -680,7 +618,6 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
       if (m + 1 < NS) prow[m + 1] += pv.y;
     }
     step_fence();
-#endif
   }
   // ---- 6. state: cur.addState(RBIS(dx))  (rbis.cpp:263-265) ----
   if constexpr (!MFMA21) state_delta();
@@ -705,16 +642,12 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
   if (r == 0) {
     double dchi[3] = { Rf[C::RB_DX + 6], Rf[C::RB_DX + 7], Rf[C::RB_DX + 8] };
     double dq[4] = { 1.0, 0.0, 0.0, 0.0 };
-#ifndef SM_SKIP_QUAT
     fold_chi(dchi, dq, k.chi_tol);  // RBIS(vec) constructor
-#endif
     double chi[3];
 #pragma unroll
     for (int i = 0; i < 3; i++) chi[i] = chi_cur[i] + dchi[i];
     double qq[4] = { q[0], q[1], q[2], q[3] };
-#ifndef SM_SKIP_QUAT
     fold_chi(chi, qq, k.chi_tol);
-#endif
     double o[4];
     quat_mul(qq, dq, o);
 #pragma unroll
@@ -729,11 +662,7 @@ __global__ __launch_bounds__(SM_THREADS, PB_SMOOTH_WG_PER_CU) void k_smooth_reg(
     for (int r2 = sc; r2 < SL::NROW; r2 += G) {
       const int c0 = SL::T.comp_of[2 * r2], c1 = SL::T.comp_of[2 * r2 + 1];
       const d2_t v2 = { U[sf * PITCH + c0], c1 >= 0 ? U[sf * PITCH + c1] : 0.0 };
-#ifdef SM_NO_STORE
-      if (v2.x == 1.2345e300) *reinterpret_cast<d2_t *>(out + srow0 + (long) r2 * 128) = v2;
-#else
       *reinterpret_cast<d2_t *>(out + srow0 + (long) r2 * 128) = v2;
-#endif
     }
   }
 }

@@ -24,34 +24,20 @@
 #include <hip/hip_runtime.h>
 
 #include "rbis_device.hpp"
-#include "rbis_lds_stream.hpp"
 
-// attribution builds (scripts/smooth_attribution.sh lane...): parts compiled OUT, results are garbage, only the time means something
-#if !defined(PB_EXPERIMENTS) && (defined(SML_SKIP_FACT) || defined(SML_SKIP_RHS) || defined(SML_SKIP_SUBST) || defined(SML_SKIP_D) || \
-                                 defined(SML_SKIP_M) || defined(SML_SKIP_FINAL) || defined(SML_SKIP_CHUNKS) || defined(SML_NO_PKLOAD) || defined(SML_NO_PSTORE) || defined(SML_TIMELINE) || \
-                                 defined(SML_WIDE) || defined(SML_SINGLE_READS) || defined(SML_FINAL_SPLIT))
-#error "the SML_* attribution flags need -DPB_EXPERIMENTS as well"
+#if defined(SML_TIMELINE) && !defined(PB_EXPERIMENTS)
+#error "SML_TIMELINE (the tile timeline, scripts/smooth_attribution.sh) is an attribution build: it needs -DPB_EXPERIMENTS as well"
 #endif
 
 namespace pb {
-
-#ifndef SM_LANE_NR15
-#define SM_LANE_NR15 4
-#endif
-#ifndef SM_LANE_CH15
-#define SM_LANE_CH15 2
-#endif
 
 template <int NS>
 struct SmoothLaneCfg {
   using L = Lay<NS>;
   using SL = Slots<NS>;
-  static constexpr int NR = (NS <= 16) ? SM_LANE_NR15 : 8;   // role waves per tile
+  static constexpr int NR = (NS <= 16) ? 4 : 8;          // role waves per tile
   static constexpr int NCOL = (NS + NR - 1) / NR;        // columns / gain rows per role
-#ifndef SM_LANE_CH21
-#define SM_LANE_CH21 3
-#endif
-  static constexpr int CH = (NS <= 16) ? SM_LANE_CH15 : SM_LANE_CH21;  // rows of M per exchange (<= NR: at most one per role)
+  static constexpr int CH = (NS <= 16) ? 2 : 3;          // rows of M per exchange (<= NR: at most one per role)
   static constexpr int NP = L::NP;
   static constexpr int O_X = NP;                         // exchange region: residual + dx first, then CH rows of M
   static constexpr int PER = O_X + CH * NS;              // doubles per lane
@@ -157,41 +143,14 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
   asm volatile("" : "+v"(sb1), "+v"(sb2));
 #define SE(e) (*(((e) < 128) ? (lds + sb + (e) * 64) : ((e) < 256) ? (lds + sb1 + ((e) - 128) * 64) : (lds + sb2 + ((e) - 256) * 64)))
 #define LANE_FENCE(after) lane_fence3(sb, sb1, sb2, after)
-  // SER(e): a READ of the factor / of D / of an exchanged row.  The backend pairs neighbouring reads into ds_read2st64_b64, which the LDS
-  // serves at half the rate of two ds_read_b64 (MI355X_MICROARCH.md, LDS table).  -DSML_SINGLE_READS makes them volatile LDS accesses,
-  // which are not paired: 107.8 / 316.0 us against 100.6 / 291.6 paired (profiles/r05_smoother_attribution.txt) -- the read rate of
-  // the LDS is not what bounds this kernel, and the ordering volatile imposes costs more than the pairing.  Paired is the default.
-#ifdef SML_SINGLE_READS
-#define SER(e) (*(volatile __attribute__((address_space(3))) double *) (__attribute__((address_space(3))) double *) &SE(e))   // (a plain volatile pointer would be a FLAT access)
-#else
-#define SER(e) SE(e)
-#endif
-#ifndef SML_NT
-#define SML_NT 0   // (round 5 experiment) non-temporal global loads and stores
-#endif
-  auto gld = [&](const double *pp) { return SML_NT ? __builtin_nontemporal_load(pp) : *pp; };
-  auto gst = [&](double *pp, double v) { if (SML_NT) __builtin_nontemporal_store(v, pp); else *pp = v; };
-  auto ldc = [&](const double *src, int comp) { return gld(src + tb + C::off_of(comp)); };  // compile-time component only
+  auto ldc = [&](const double *src, int comp) { return src[tb + C::off_of(comp)]; };  // compile-time component only
   // column t of this role from one of the checkpoints: the offsets come in with wide scalar loads, the n loads go out back to back
   auto ld_col = [&](const double *src, int t, int i0, double (&v)[NS]) {  // rows i0 .. n-1 (the others: 0)
     int o[NS];
 #pragma unroll
     for (int i = 0; i < NS; i++) o[i] = tab.col[w][t][i];
-#ifdef SML_WIDE   // attribution (round 5): the SAME loads as whole 16-byte rows -- every byte of every 128-byte line the instruction touches is
-                  // fetched by it, where the 8-byte access at a 16-byte stride uses half of each.  Results are garbage.
 #pragma unroll
-    for (int i = 0; i < NS; i++) {
-      if (i >= i0) {
-        const d2_t r = *reinterpret_cast<const d2_t *>(src + tb + (o[i] & ~1));
-        v[i] = r.x + r.y;
-      } else {
-        v[i] = 0.0;
-      }
-    }
-#else
-#pragma unroll
-    for (int i = 0; i < NS; i++) v[i] = (i >= i0) ? gld(src + tb + o[i]) : 0.0;
-#endif
+    for (int i = 0; i < NS; i++) v[i] = (i >= i0) ? src[tb + o[i]] : 0.0;
   };
 
   int cidx[NCOL], cc[NCOL];  // this role's columns (gain rows); stand-ins mirror column n - 1
@@ -218,66 +177,18 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
     for (int i = 0; i < NS; i++) rv[i] = ldc(next_sm, L::OFF_VEC + i) - ldc(next_pred, L::OFF_VEC + i);
   }
 
-  // (round 5 experiment, OFF) the role's columns of P_k and the filtered state for step 2 asked for HERE, so that they arrive behind the
-  // factorisation (the barriers order LDS only, nothing waits for them on the way): SML_EARLY_PK = how many of the role's 3 columns
-  // (21 states only).  Measured at 64k filters: 0: 291.6 us, 1: 303.2 (20 B of scratch), 2: 311.3 (60 B), 3: 339.4 (276 B) -- the
-  // kernel has no registers left for them.
-#ifndef SML_EARLY_PK
-#define SML_EARLY_PK 0
-#endif
-  constexpr int NEARLY = (NS == 21) ? SML_EARLY_PK : 0;
-  constexpr bool EARLY_PK = NEARLY > 0;
-  double pke[EARLY_PK ? NEARLY : 1][EARLY_PK ? NS : 1], ske[10];
   // ---- 1. P^- = L diag(d) L^T ----
   {
     double a[NCOL][NS];
-    // SML_ROWTOP (21 states): P^- comes in by whole 16-byte rows (role w: rows w, w + NR, ...; the table of step 4) into the factor's place,
-    // and every role takes its columns from there -- 17 full-line loads per role instead of 39 eight-byte ones that use half of every
-    // line they touch.  Measured: 292.1 against 291.1 us, the tile's first barrier still comes 14 k cycles in -- every CU asks for its
-    // tile's 129 KB at the same moment (four dispatch rounds in lockstep): the burst is bound by the memory, not by the form of the loads,
-    // and this kernel has neither registers nor LDS to ask earlier.  Off.
-#ifndef SML_ROWTOP
-#define SML_ROWTOP 0
-#endif
-    constexpr bool ROWTOP = (NS == 21) && SML_ROWTOP;
-    if constexpr (ROWTOP) {
-      d2_t rr[C::RU];
 #pragma unroll
-      for (int u = 0; u < C::RU; u++) {
-        const int r2 = (w + NR * u < SL::NROW) ? w + NR * u : SL::NROW - 1;
-        rr[u] = *reinterpret_cast<const d2_t *>(next_pred + tb + r2 * 128);
-      }
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int u = 0; u < C::RU; u++) {
-        const int e0 = tab.drow[w][u][0], e1 = tab.drow[w][u][1];
-        if (e0 >= 0) S[e0 * 64] = rr[u].x;
-        if (e1 >= 0) S[e1 * 64] = rr[u].y;
-      }
-      lds_barrier();
-#pragma unroll
-      for (int t = 0; t < NCOL; t++)
-#pragma unroll
-        for (int i = 0; i < NS; i++) a[t][i] = (i >= NR * t) ? S[pk_s(i, cc[t]) * 64] : 0.0;   // (above the column's diagonal: never used)
-    } else {
-#pragma unroll
-      for (int t = 0; t < NCOL; t++) ld_col(next_pred, t, NR * t, a[t]);  // column w + NR t: rows above NR t are above its diagonal for every role
-    }
-    if constexpr (EARLY_PK) {
-#pragma unroll
-      for (int i = 0; i < 6; i++) ske[i] = ldc(cur, L::OFF_VEC + i);
-#pragma unroll
-      for (int i = 0; i < 4; i++) ske[6 + i] = ldc(cur, L::OFF_QUAT + i);
-#pragma unroll
-      for (int t = 0; t < NEARLY; t++) ld_col(cur, t, 0, pke[t]);
-    }
+    for (int t = 0; t < NCOL; t++) ld_col(next_pred, t, NR * t, a[t]);  // column w + NR t: rows above NR t are above its diagonal for every role
     __builtin_amdgcn_sched_barrier(0);
     if constexpr (NS == 21) {  // rbis.cpp:244-251: a bias block whose variance is < 1e-11 is replaced by I in the factorised matrix
       bool fix_g = false, fix_a = false;
 #pragma unroll
       for (int i = 0; i < 3; i++) {
-        fix_g = fix_g | ((ROWTOP ? SE(pk(15 + i, 15 + i)) : ldc(next_pred, L::OFF_P + pk(15 + i, 15 + i))) < .00000000001);
-        fix_a = fix_a | ((ROWTOP ? SE(pk(18 + i, 18 + i)) : ldc(next_pred, L::OFF_P + pk(18 + i, 18 + i))) < .00000000001);
+        fix_g = fix_g | (ldc(next_pred, L::OFF_P + pk(15 + i, 15 + i)) < .00000000001);
+        fix_a = fix_a | (ldc(next_pred, L::OFF_P + pk(18 + i, 18 + i)) < .00000000001);
       }
 #pragma unroll
       for (int t = 0; t < NCOL; t++)
@@ -290,10 +201,6 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
     double inv_prev = 0.0;
     static_for<NS>([&](auto KK) {
       constexpr int kk = decltype(KK)::value;
-#ifdef SML_SKIP_FACT
-      if (kk == 0) S[0] = a[0][0] + a[NCOL - 1][NS - 1];
-      return;
-#endif
       if (w == kk % NR) {  // owner of column kk
         constexpr int t = kk / NR;
         const double d = a[t][kk];
@@ -310,7 +217,7 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
       if constexpr (kk > 0)
         if (w == (kk - 1) % NR) SE(pk(kk - 1, kk - 1)) = inv_prev;
       if constexpr (kk + 1 < NS) {
-        const double dk = SER(pk(kk, kk));
+        const double dk = SE(pk(kk, kk));
         // column slot t holds a column c in [NR t, NR t + NR): it is finished once kk >= NR (t + 1) - 1, and its rows above NR t
         // are above the diagonal -- neither is touched (compile-time bounds; what remains above the diagonal is never read)
         double tc[NCOL];
@@ -319,7 +226,7 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
           if (kk < NR * (t + 1) - 1) tc[t] = S[pk_s(cc[t], kk) * 64] * dk;
 #pragma unroll
         for (int i = kk + 1; i < NS; i++) {
-          const double lik = SER(pk(i, kk));
+          const double lik = SE(pk(i, kk));
 #pragma unroll
           for (int t = 0; t < NCOL; t++)
             if (kk < NR * (t + 1) - 1 && i >= NR * t) {
@@ -344,22 +251,17 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
     double wv[3], v[3], q[4], R[9];
 #pragma unroll
     for (int i = 0; i < 3; i++) {
-      wv[i] = EARLY_PK ? ske[i] : ldc(cur, L::OFF_VEC + i);
-      v[i] = EARLY_PK ? ske[3 + i] : ldc(cur, L::OFF_VEC + 3 + i);
+      wv[i] = ldc(cur, L::OFF_VEC + i);
+      v[i] = ldc(cur, L::OFF_VEC + 3 + i);
     }
 #pragma unroll
-    for (int i = 0; i < 4; i++) q[i] = EARLY_PK ? ske[6 + i] : ldc(cur, L::OFF_QUAT + i);
+    for (int i = 0; i < 4; i++) q[i] = ldc(cur, L::OFF_QUAT + i);
     quat_to_rot(q, R);
     const double gb[3] = { -k.g * R[6], -k.g * R[7], -k.g * R[8] };
 #pragma unroll
     for (int t = 0; t < NCOL; t++) {
       double p[NS];
-      if (t < NEARLY) {   // (compile-time inside the unrolled loop)
-#pragma unroll
-        for (int i = 0; i < NS; i++) p[i] = pke[t < NEARLY ? t : 0][i];
-      } else {
-        ld_col(cur, t, 0, p);
-      }
+      ld_col(cur, t, 0, p);
 #pragma unroll
       for (int i = 0; i < NS; i++) z[t][i] = p[i];
       const double pv[3] = { p[3], p[4], p[5] }, pc[3] = { p[6], p[7], p[8] };
@@ -387,68 +289,19 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
   lds_barrier();  // the factor is complete (the last reciprocal pivots were written behind the last barrier of step 1)
   SML_T(3);
 
-  // (round 5 experiment) the first half of the rows of step 4 requested HERE, in front of the substitutions, so that they arrive behind
-  // them (the barriers order LDS only): SML_EARLY_D, 21 states.  Measured: 304.5 us against 291.5 (100 B of scratch): off.
-#ifndef SML_EARLY_D
-#define SML_EARLY_D 0
-#endif
-  constexpr bool EARLY_D = (NS == 21) && SML_EARLY_D;
-  constexpr int RH_E = (C::RU + 1) / 2;
-  d2_t dse[EARLY_D ? RH_E : 1], dpe[EARLY_D ? RH_E : 1];
-  if constexpr (EARLY_D) {
-#pragma unroll
-    for (int v = 0; v < RH_E; v++) {
-      const int r2 = (v < C::RU && w + NR * v < SL::NROW) ? w + NR * v : SL::NROW - 1;
-      dse[v] = *reinterpret_cast<const d2_t *>(next_sm + tb + r2 * 128);
-      dpe[v] = *reinterpret_cast<const d2_t *>(next_pred + tb + r2 * 128);
-    }
-  }
   // ---- 3. (P^-) X = Ad P_k out of the LDS factor: z[t][:] becomes row cidx[t] of G ----
-  // SML_STREAM (21 states): the reads as lds_stream's explicit pipeline of SINGLE ds_read_b64 (rbis_lds_stream.hpp) -- with 8 roles every
-  // entry of the factor is read 8 times, and the paired ds_read2st64_b64 the backend makes of neighbouring reads moves the same bytes in
-  // twice the LDS time (8 x 462 reads x 8 cycles per pair = 15 k of the substitutions' 17 k cycles).  Measured: the substitutions take
-  // 15.1 k instead of 17.2 k cycles and step 4 waits 2 k longer for its rows: 290.7 against 291.1 us per step.  Off.
-#ifndef SML_STREAM
-#define SML_STREAM 0
-#endif
-  constexpr bool STREAM = (NS == 21) && SML_STREAM;
-  const LdsBases lbb{ lane * 8, lane * 8 + 128 * 512, lane * 8 + 256 * 512 };   // (dynamic LDS starts at 0: no static LDS in this kernel)
-#ifndef SML_SKIP_SUBST
-  if constexpr (STREAM) {
-    auto pin_z = [&](auto) {
-#pragma unroll
-      for (int t = 0; t < NCOL; t++)
-#pragma unroll
-        for (int i = 0; i < NS; i++) lane_pin(z[t][i]);
-    };
-    lds_stream<NS *(NS - 1) / 2, SmwLowerByColumn<NS>>(lbb, [&](auto KQ, double l) {
-      constexpr int kq = decltype(KQ)::value, i = SmwLowerByColumn<NS>::row(kq), mm = SmwLowerByColumn<NS>::col(kq);
-#pragma unroll
-      for (int t = 0; t < NCOL; t++) z[t][i] = fma(-l, z[t][mm], z[t][i]);
-    }, pin_z);
-    lds_stream<NS, SmwDiag>(lbb, [&](auto KQ, double inv) {
-      constexpr int i = decltype(KQ)::value;
-#pragma unroll
-      for (int t = 0; t < NCOL; t++) z[t][i] *= inv;
-    }, pin_z);
-    lds_stream<NS *(NS - 1) / 2, SmwUpperByColumn<NS>>(lbb, [&](auto KQ, double l) {
-      constexpr int kq = decltype(KQ)::value, i = SmwUpperByColumn<NS>::ci(kq), mm = SmwUpperByColumn<NS>::cm(kq);
-#pragma unroll
-      for (int t = 0; t < NCOL; t++) z[t][i] = fma(-l, z[t][mm], z[t][i]);
-    }, pin_z);
-  } else {
 #pragma unroll
   for (int i = 1; i < NS; i++)
 #pragma unroll
     for (int m = 0; m < i; m++) {
-      const double l = SER(pk(i, m));
+      const double l = SE(pk(i, m));
 #pragma unroll
       for (int t = 0; t < NCOL; t++) z[t][i] = fma(-l, z[t][m], z[t][i]);
       if (m == i - 1 && (i & 1)) LANE_FENCE(z[0][i >= 2 ? i - 2 : 0]);  // (row i - 2: one group of reads may run ahead)
     }
 #pragma unroll
   for (int i = 0; i < NS; i++) {
-    const double inv = SER(pk(i, i));
+    const double inv = SE(pk(i, i));
 #pragma unroll
     for (int t = 0; t < NCOL; t++) z[t][i] *= inv;
   }
@@ -457,20 +310,18 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
   for (int i = NS - 2; i >= 0; i--)
 #pragma unroll
     for (int m = i + 1; m < NS; m++) {
-      const double l = SER(pk(m, i));
+      const double l = SE(pk(m, i));
 #pragma unroll
       for (int t = 0; t < NCOL; t++) z[t][i] = fma(-l, z[t][m], z[t][i]);
       if (m == NS - 1 && (i & 1)) LANE_FENCE(z[0][i + 2 < NS ? i + 2 : NS - 1]);
     }
-  }
-#endif
   // dx = G resid (rbis.cpp:263): this role's entries
   double dxv[NCOL];
 #pragma unroll
   for (int t = 0; t < NCOL; t++) dxv[t] = 0.0;
 #pragma unroll
   for (int i = 0; i < NS; i++) {
-    const double r = SER(O_X + i);
+    const double r = SE(O_X + i);
 #pragma unroll
     for (int t = 0; t < NCOL; t++) dxv[t] = fma(z[t][i], r, dxv[t]);
   }
@@ -497,13 +348,8 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
       for (int v = 0; v < RH; v++) {
         const int u = pass * RH + v;
         const int r2 = (u < C::RU && w + NR * u < SL::NROW) ? w + NR * u : SL::NROW - 1;
-        if (EARLY_D && pass == 0) {
-          ds[v] = dse[EARLY_D ? v : 0];
-          dp[v] = dpe[EARLY_D ? v : 0];
-        } else {
-          ds[v] = *reinterpret_cast<const d2_t *>(next_sm + tb + r2 * 128);
-          dp[v] = *reinterpret_cast<const d2_t *>(next_pred + tb + r2 * 128);
-        }
+        ds[v] = *reinterpret_cast<const d2_t *>(next_sm + tb + r2 * 128);
+        dp[v] = *reinterpret_cast<const d2_t *>(next_pred + tb + r2 * 128);
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -548,9 +394,6 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
   }
 
   // ---- 6. P^s = P_k + G D G^T, CH rows of M = G D at a time ----
-#ifdef SML_SKIP_CHUNKS
-  if (B > 0) return;
-#endif
   double pkn[NCOL][CH];
   int pon[NCOL][CH];
 #pragma unroll
@@ -576,28 +419,11 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
         pkv[t][q] = pkn[t][q];
         po[t][q] = pon[t][q];
         pon[t][q] = tab.col[w][t][(c0 + CH + q < NS) ? c0 + CH + q : NS - 1];
-#ifdef SML_NO_PKLOAD
-        pkn[t][q] = 1.0;
-#elif defined(SML_WIDE)
-        {
-          const d2_t r = *reinterpret_cast<const d2_t *>(cur + tb + (pon[t][q] & ~1));
-          pkn[t][q] = r.x + r.y;
-        }
-#else
-        pkn[t][q] = gld(cur + tb + pon[t][q]);
-#endif
+        pkn[t][q] = cur[tb + pon[t][q]];
       }
 #pragma unroll
     for (int t = 0; t < NCOL; t++) {
       const int rel = cidx[t] - c0;
-#ifdef SML_SKIP_M
-      if (rel >= 0 && rel < CH && cidx[t] < NS) {
-        mcc = rel;
-#pragma unroll
-        for (int j = 0; j < NS; j++) m[j] = z[t][j];
-      }
-      continue;
-#endif
       if (rel >= 0 && rel < CH && cidx[t] < NS) {
         mcc = rel;
         double hook = z[t][0];
@@ -607,7 +433,7 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
         for (int i = 0; i < NS; i++)
 #pragma unroll
           for (int j = 0; j <= i; j++) {
-            const double d = SER(pk(i, j));
+            const double d = SE(pk(i, j));
             m[j] = fma(z[t][i], d, m[j]);
             if (i != j) m[i] = fma(z[t][j], d, m[i]);
             if (j == i && (i & 1)) {  // end of a group of two rows of D
@@ -636,41 +462,21 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
     tl[10] = __builtin_amdgcn_s_memtime();
     tl[8] += tl[10] - ta;
 #endif
-#ifdef SML_SKIP_FINAL
-    continue;
-#endif
 #pragma unroll
     for (int q = 0; q < CH; q++) {
       const int c = c0 + q;
       if (c < NS && c <= cidx[NCOL - 1]) {  // (wave-uniform) some row of this role is at or below the diagonal of column c
         double mr[NS];
 #pragma unroll
-        for (int j = 0; j < NS; j++) mr[j] = SER(O_X + q * NS + j);
+        for (int j = 0; j < NS; j++) mr[j] = SE(O_X + q * NS + j);
 #pragma unroll
         for (int t = 0; t < NCOL; t++) {
           const int r = cidx[t];
           if (r < NS && c <= r) {
-#ifdef SML_FINAL_SPLIT   // attribution (round 5): the sum in three interleaved parts -- a multiply-add that waits for its predecessor costs twice its slot
-            double acc = pkv[t][q], acc1 = 0.0, acc2 = 0.0;
-#pragma unroll
-            for (int j = 0; j < NS; j += 3) {
-              acc = fma(z[t][j], mr[j], acc);
-              if (j + 1 < NS) acc1 = fma(z[t][j + 1], mr[j + 1], acc1);
-              if (j + 2 < NS) acc2 = fma(z[t][j + 2], mr[j + 2], acc2);
-            }
-            acc += acc1 + acc2;
-#else
             double acc = pkv[t][q];
 #pragma unroll
             for (int j = 0; j < NS; j++) acc = fma(z[t][j], mr[j], acc);
-#endif
-#ifdef SML_NO_PSTORE
-            if (acc == 1.2345e300) out[tb + po[t][q]] = acc;
-#elif defined(SML_WIDE)
-            if (active) *reinterpret_cast<d2_t *>(out + tb + (po[t][q] & ~1)) = d2_t{ acc, acc };
-#else
-            if (active) gst(out + tb + po[t][q], acc);
-#endif
+            if (active) out[tb + po[t][q]] = acc;
           }
         }
       }
@@ -685,7 +491,6 @@ __global__ __launch_bounds__(SmoothLaneCfg<NS>::THREADS, SmoothLaneCfg<NS>::WAVE
 
 #undef S
 #undef SE
-#undef SER
 #undef LANE_FENCE
 
 }  // namespace pb

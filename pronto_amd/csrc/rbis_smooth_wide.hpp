@@ -26,6 +26,7 @@
 
 #include "rbis_device.hpp"
 #include "rbis_kernels.hpp"
+#include "rbis_lds_stream.hpp"
 #include "rbis_smooth_lane.hpp"
 
 namespace pb {

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of the pair kernels at 64k filters: every variant (a list of VAR=value settings, "-" = none) is run REPS times, interleaved,
-# and the minimum per row is printed -- single runs on this pool scatter by 1-3 us.   bash scripts/leg_ab.sh 3 - PRONTO_BATCH_LEGPLAN=0
+# and the minimum per row is printed -- single runs on this pool scatter by 1-3 us.   bash scripts/leg_ab.sh 3 - PRONTO_BATCH_MEMHINT=0
 REPS=$1; shift
 OUT=${GRAFT_REPO_ROOT:-/root/repo}/gpurun_out/r04/leg_ab
 mkdir -p $OUT; rm -f $OUT/*.txt
