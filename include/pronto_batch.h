@@ -484,11 +484,14 @@ int pb_set_output_slot(pb_ctx *ctx, int slot);
  * rbis.cpp:234-266).  One-shot, like pb_set_output_slot: the NEXT pb_step_legodo / pb_step_legodo_split also writes the posterior
  * of its process step -- what pb_predict alone would leave from the same head: bit for bit for 15 states, to rounding
  * (1e-16 relative) for 21 -- into checkpoint `slot`, and consumes the
- * setting whatever its outcome.  Combines with pb_set_output_slot: one call reads the head and writes two slots.  The filtered
+ * setting whatever its outcome.  pb_step_legodo_correct takes it too, for both correction kinds and with the same contract, when an
+ * output slot is pending as well (a checkpointed step: the INS posterior into `slot`, the posterior of the step's last measurement
+ * into the output slot -- the two EKFSmoothBackwardsPass reads); with a predicted slot alone it refuses as the calls below.  15 states:
+ * ONE launch (k_step_coop_corr_pred); 21 states: the fused step's launch writes the slot and the correction follows as its own launch.  Combines with pb_set_output_slot: one call reads the head and writes two slots.  The filtered
  * posterior is bit-identical to the same call without a predicted slot.  The 15-state two-wave step, the four-wave 21-state step and the
  * two-wave 21-state step (PRONTO_BATCH_QUAD21=0) write both in ONE launch (k_step_quad_pred, k_step_coop_pred); k_step<15> (beyond
  * 393 216 filters) runs the predict into the slot and the fused step as two launches.  PB_ERR_ARG: slot out of range, the pending output slot, or the slot the head lives in.
- * pb_predict, pb_update_indexed*, pb_step_legodo_correct / _joints / _feet, pb_run_legodo and pb_replay_legodo_fused /
+ * pb_predict, pb_update_indexed*, pb_step_legodo_joints / _feet, pb_run_legodo and pb_replay_legodo_fused /
  * _checkpointed with a predicted slot pending: PB_ERR_STATE (and the setting is cleared).  slot = -1 cancels. */
 int pb_set_pred_slot(pb_ctx *ctx, int slot);
 /* the checkpoint slot the head currently lives in, or -1 (the context's own array) */
@@ -553,6 +556,37 @@ int pb_smooth_log(pb_ctx *ctx, int n_steps, int stride, const double *imu_stream
  * over) and no output / predicted slot is pending. */
 int pb_smooth_log_fused(pb_ctx *ctx, int n_steps, int stride, const double *imu_stream, const double *lo_stream, const uint8_t *mask_stream,
                         const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms);
+
+/* pb_smooth_log / pb_smooth_log_fused for a log with a sparse stream of corrections behind some of its IMU + leg-odometry pairs: the
+ * 6-DoF visual-odometry position_orient (PB_CORR_POS_ORIENT) or the scan-match position_yaw (PB_CORR_POS_YAW) of
+ * pb_step_legodo_correct.  EKFSmoothBackwardsPass takes as "cur" the posterior of the LAST measurement behind an INS update
+ * (mav_state_est.cpp:98-189), however many there were; so the step's filtered posterior is the one behind its correction.
+ * A step with a tick: fused = 1, one pb_step_legodo_correct (in the recompute pass with the window's predicted and filtered slots
+ * set: one launch for 15 states, two for 21); fused = 0, pb_predict, pb_update_indexed and pb_update_indexed_orient into the same
+ * filtered slot -- the per-message kernels.  A step without a tick is the step of pb_smooth_log_fused / pb_smooth_log.  Slots
+ * (pb_smooth_log_slots), sink order, head afterwards, error contract and elapsed_ms are theirs; corr == NULL or n_ticks == 0 IS
+ * pb_smooth_log_fused / pb_smooth_log, bit for bit.  The recompute pass re-applies the same correction blocks, so the smoothed
+ * posteriors are, bit for bit, those of the all-checkpoints pass built from the same calls (fused: pb_set_pred_slot +
+ * pb_set_output_slot + pb_step_legodo_correct + pb_smooth_step); fused and un-fused agree to the rounding stated at
+ * pb_step_legodo_correct.  PB_ERR_ARG, the head left usable in the context's own array: an unknown kind, a step list that is not
+ * strictly increasing or leaves [0, n_steps), NULL step / z2 / R2 / quat_meas2 with n_ticks > 0, an R2 that is not diagonal.
+ * position_orient: the measurement is the caller's COMPOSED pose T1 = T0 o delta, and T0 depends on the filter's posterior at the key
+ * frame (rbis_fovis_update.cpp:184-223): the blocks come from a forward run (pb_snapshot* / pb_compose_delta) or from a synthetic
+ * stream; this call composes nothing.  A scan-match position_yaw is absolute and needs no such step. */
+typedef struct pb_corr_stream {
+  int kind;                  /* PB_CORR_POS_ORIENT | PB_CORR_POS_YAW; m = 6 | 4 */
+  int n_ticks;               /* 0 is allowed */
+  const int32_t *step;       /* HOST int32[n_ticks], strictly increasing, each in [0, n_steps): the correction
+                                follows the IMU + leg-odometry pair of that step */
+  const double *z2;          /* device [n_ticks][m][B] */
+  const double *R2;          /* device [n_ticks][m][B] (PB_R_DIAG) or host double[m] (PB_R_DIAG_BROADCAST) */
+  int r_kind2;
+  const double *quat_meas2;  /* device [n_ticks][4][B] */
+  const uint8_t *mask2;      /* device [n_ticks][B] or NULL */
+} pb_corr_stream;
+int pb_smooth_log_corrected(pb_ctx *ctx, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
+                            const uint8_t *mask_stream, const double q[4], double dt, int first_slot, const pb_corr_stream *corr,
+                            int fused, pb_smooth_sink sink, void *user, float *elapsed_ms);
 
 /* ---- estimator queries (mav_state_est.hpp:20-22) -------------------------------------------------------- */
 

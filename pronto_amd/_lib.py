@@ -40,6 +40,12 @@ def build(force=False):
     return LIB_PATH
 
 
+class CorrStream(C.Structure):
+    """pb_corr_stream (pb_smooth_log_corrected)"""
+    _fields_ = [("kind", C.c_int), ("n_ticks", C.c_int), ("step", C.c_void_p), ("z2", C.c_void_p), ("R2", C.c_void_p), ("r_kind2", C.c_int),
+                ("quat_meas2", C.c_void_p), ("mask2", C.c_void_p)]
+
+
 _lib = None
 
 _dp = C.POINTER(C.c_double)
@@ -77,6 +83,8 @@ _SIGS = {
                                 C.POINTER(C.c_float)]),
     "pb_smooth_log_fused": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_double, C.c_int, C.c_void_p,
                                       C.c_void_p, C.POINTER(C.c_float)]),
+    "pb_smooth_log_corrected": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_double, C.c_int, C.c_void_p,
+                                          C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]),
     "pb_set_head": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_predict": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_int]),
     "pb_update_indexed": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,

@@ -131,8 +131,9 @@ class BatchEstimator:
         self._chk(self._L.pb_set_output_slot(self._h, int(slot)))
 
     def set_pred_slot(self, slot):
-        """The next step_legodo / step_legodo_split also writes its INS posterior (the prediction, before the leg-odometry update)
-        into checkpoint `slot`.  One-shot: that call consumes it whatever its outcome.  -1 cancels."""
+        """The next step_legodo / step_legodo_split -- or step_legodo_correct with an output slot pending as well -- also writes its INS
+        posterior (the prediction, before the leg-odometry update) into checkpoint `slot`.  One-shot: that call consumes it whatever
+        its outcome.  -1 cancels."""
         self._chk(self._L.pb_set_pred_slot(self._h, int(slot)))
 
     def state_save(self, slot):
@@ -180,6 +181,54 @@ class BatchEstimator:
     def smooth_log_fused(self, imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot=0, sink=None, timed=False):
         """smooth_log on pb_smooth_log_fused: every forward and recompute step is ONE fused launch (step_legodo's semantics)."""
         return self.smooth_log(imu_stream, lo_stream, mask_stream, q4, dt, stride, first_slot, sink, timed, fused=True)
+
+    def smooth_log_corrected(self, imu_stream, lo_stream, mask_stream, q4, dt, stride, corr_kind, corr_steps, z2, R2, quat_meas2, mask2=None,
+                             fused=True, first_slot=0, sink=None, timed=False):
+        """smooth_log / smooth_log_fused for a log with corrections behind some of its pairs (pb_smooth_log_corrected): corr_kind as
+        step_legodo_correct (m = 6 / 4), corr_steps the strictly increasing steps that carry one, z2 [n_ticks, m, B], quat_meas2
+        [n_ticks, 4, B], mask2 [n_ticks, B] or None (device tensors), R2 a device tensor [n_ticks, m, B] or a length-m list (one
+        diagonal for every tick and filter).  corr_steps = None or empty: no correction stream at all."""
+        T = imu_stream.shape[0]
+        pi, m1 = _ptr(imu_stream, shape=(T, 7, self.B))
+        pl, m2 = _ptr(lo_stream, shape=(T, 6, self.B))
+        pm, m3 = _ptr(mask_stream, np.uint8, shape=(T, self.B))
+        if _same_mem(m1, m2, m3) != PB_DEVICE:
+            raise ValueError("smooth_log_corrected needs device-resident streams")
+        cs, keep = None, []
+        if corr_steps is not None:
+            steps = np.ascontiguousarray(corr_steps, dtype=np.int32).reshape(-1)
+            nt = steps.shape[0]
+            m = {_lib.PB_CORR_POS_ORIENT: 6, _lib.PB_CORR_POS_YAW: 4}.get(corr_kind)   # (None: an unknown kind is the library's to refuse)
+            cs = _lib.CorrStream(kind=int(corr_kind), n_ticks=nt, step=steps.ctypes.data)
+            keep.append(steps)
+            mems = []
+            if nt > 0:
+                pz, mz = _ptr(z2, shape=m and (nt, m, self.B))
+                pq, mq = _ptr(quat_meas2, shape=(nt, 4, self.B))
+                pk, mk = _ptr(mask2, np.uint8, shape=(nt, self.B))
+                mems = [mz, mq, mk]
+                if _is_torch(R2):
+                    pr, mr = _ptr(R2, shape=m and (nt, m, self.B))
+                    mems.append(mr)
+                    cs.r_kind2 = _lib.PB_R_DIAG
+                else:
+                    rb = np.ascontiguousarray(R2, dtype=np.float64)
+                    if m and rb.shape != (m,):
+                        raise ValueError("R2: a device tensor [n_ticks, m, B] or m values")
+                    keep.append(rb)
+                    pr = C.c_void_p(rb.ctypes.data)
+                    cs.r_kind2 = _lib.PB_R_DIAG_BROADCAST
+                if any(x is not None and x != PB_DEVICE for x in mems):
+                    raise ValueError("smooth_log_corrected needs device-resident correction blocks")
+                cs.z2, cs.R2, cs.quat_meas2, cs.mask2 = pz, pr, pq, pk
+        q = (C.c_double * 4)(*q4)
+        ms = C.c_float(0)
+        SINK = C.CFUNCTYPE(None, C.c_void_p, C.c_int, C.c_int)
+        cb = SINK((lambda user, step, slot: sink(step, slot))) if sink is not None else None
+        self._chk(self._L.pb_smooth_log_corrected(self._h, T, stride, pi, pl, pm, q, dt, first_slot, C.byref(cs) if cs is not None else None,
+                                                  1 if fused else 0, C.cast(cb, C.c_void_p) if cb else None, None,
+                                                  C.byref(ms) if timed else None))
+        return ms.value if timed else None
 
     def get_slot(self, slot, first=0, count=None, want_cov=True):
         """get_head for a posterior that lives in a checkpoint slot."""

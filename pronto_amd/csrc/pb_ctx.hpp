@@ -1,6 +1,6 @@
 // pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so
-// (the kernels are instantiated in fourteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip
-// and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
+// (the kernels are instantiated in fifteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// pb_step_corr_pred.hip and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
 // pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip; pb_yawlock.hip;
 // pronto_batch.hip the C ABI and the rest).
 #pragma once
@@ -176,7 +176,12 @@ int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, cons
 // such kernel (pbk_step then runs the predict into `pred` and the fused step as two launches)
 int pbk_step_pred_kernel(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                          const StepBcast &bc);
-// predict + leg-odometry update + a second (orientation) update in one state round trip; corr_kind = enum pb_corr
+// pb_step_corr_pred.hip: the 15-state fused step with a correction stage that also writes its predicted posterior into `pred`
+// (k_step_coop_corr_pred); -1 = not a 15-state context
+int pbk_step_corr_pred_kernel(pb_ctx *c, int corr_kind, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask,
+                              const double q[4], const CorrArgs &ca, const StepBcast &bc);
+// predict + leg-odometry update + a second (orientation) update in one state round trip; corr_kind = enum pb_corr.  A pending predicted
+// slot (c->pred_slot) is consumed: the INS posterior goes there as well
 int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                      const double *z2, const double *r2, const double *rb2, const double *qm2, const uint8_t *mask2,
                      const StepBcast *bcast = nullptr, const double *zb = nullptr, const double *qb = nullptr);

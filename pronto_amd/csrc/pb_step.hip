@@ -161,7 +161,8 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
   if (c->ns == 21) {
     // 21 states: role C's 15 x 15 sub-matrix already fills the register file (256 VGPR + 242 AGPR for the plain step); a
     // second update stage in the same kernel spills 550-690 bytes per lane and measured SLOWER than two launches.  Same
-    // arithmetic as two launches: the fused step, then the correction alone on the cooperative update kernel.
+    // arithmetic as two launches: the fused step, then the correction alone on the cooperative update kernel.  A pending predicted
+    // slot is the first launch's (k_step_quad_pred / k_step_coop_pred<21>); the correction lands in the output slot.
     int rc = pbk_step(c, true, imu, lo, mask, q, bcast);
     if (rc) return rc;
     static const int idx_po[6] = { 9, 10, 11, 6, 7, 8 }, idx_py[4] = { 9, 10, 11, 8 };
@@ -185,14 +186,21 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
     for (int i = 0; i < 4; i++) ca.qb2[i] = qb[i];
   }
   const StepBcast bc = bcast ? *bcast : StepBcast();
+  // a predicted slot pending (pb_set_pred_slot, consumed here): the kernel that also stores the INS posterior (pb_step_corr_pred.hip)
+  double *pred = c->pred_slot >= 0 ? c->hist + (size_t) c->pred_slot * c->state_doubles : nullptr;
+  c->pred_slot = -1;
   double *out = update_target(c);
   int rc = PB_OK;
   imu = pbk_idle_prepare(c, imu, &rc);
   if (rc) return rc;
-  with_mem_hint(c->mem_hint, [&](auto mh) {
-    if (corr_kind == PB_CORR_POS_ORIENT) launch_corr<15, decltype(mh)::value, CorrPosOrient>(c, out, imu, lo, mask, q, ca, bc);
-    else launch_corr<15, decltype(mh)::value, CorrPosYaw>(c, out, imu, lo, mask, q, ca, bc);
-  });
+  if (pred) {
+    if (pbk_step_corr_pred_kernel(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc)) return fail(c, PB_ERR_STATE, "pb_step_legodo_correct: no kernel keeps the prediction here");
+  } else {
+    with_mem_hint(c->mem_hint, [&](auto mh) {
+      if (corr_kind == PB_CORR_POS_ORIENT) launch_corr<15, decltype(mh)::value, CorrPosOrient>(c, out, imu, lo, mask, q, ca, bc);
+      else launch_corr<15, decltype(mh)::value, CorrPosYaw>(c, out, imu, lo, mask, q, ca, bc);
+    });
+  }
   LAUNCHCHK(c);
   update_done(c, out);
   return PB_OK;

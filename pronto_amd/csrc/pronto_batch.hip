@@ -414,7 +414,7 @@ static int stage_in(pb_ctx *c, int mem, Part *parts, int n)
 // ---- the per-call contract: what an entry point takes from the context, declared in ONE line at its top -- CALL(c, flags) ----
 // The one-shot inputs belong to the NEXT call that takes them, whatever becomes of it: the pb_set_imu_valid mask to the next call that
 // takes an IMU step, the per-filter message times / validity (pb_legodo_set_message_times) to the next odometry or pair call,
-// pb_set_pred_slot to the next pb_step_legodo / pb_step_legodo_split.  The guard takes them FIRST, before anything is validated, so
+// pb_set_pred_slot to the next pb_step_legodo / pb_step_legodo_split / pb_step_legodo_correct.  The guard takes them FIRST, before anything is validated, so
 // that a call that fails early cannot leave them behind for an unrelated later call, and forgets them when the call returns.
 enum : unsigned {
   IMU_STEP = 1,      // takes the IMU validity mask: held in imu_valid_cur for the duration of the call (pbk_idle_prepare)
@@ -423,6 +423,7 @@ enum : unsigned {
   PRED_REFUSE = 8,   // takes an IMU step or an update but writes no predicted posterior: with a slot pending it refuses and forgets it
   PRED_FORGET = 16,  // runs a whole log of steps with predicted slots of its own: a pending one is forgotten
   NEEDS_STATE = 32,  // PB_ERR_STATE before pb_reset
+  PRED_WITH_OUT = 64,  // (with PRED_TAKE) a checkpointed step only: a predicted slot without a pending output slot is refused as by PRED_REFUSE
 };
 struct LegMsgTimes {
   const int64_t *utimes = nullptr;
@@ -461,7 +462,11 @@ struct Call {
     if ((what & (PRED_REFUSE | PRED_FORGET)) && c->pred_slot >= 0) {
       c->pred_slot = -1;
       if (what & PRED_REFUSE)
-        return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / pb_step_legodo_split)", fn);
+        return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / _split / _correct)", fn);
+    }
+    if ((what & PRED_WITH_OUT) && c->pred_slot >= 0 && c->out_slot < 0) {
+      c->pred_slot = -1;
+      return fail(c, PB_ERR_STATE, "%s: no predicted slot here without an output slot (pb_set_output_slot)", fn);
     }
     if ((what & NEEDS_STATE) && !c->have_state) return fail(c, PB_ERR_STATE, "%s before pb_reset", fn);
     // the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
@@ -651,7 +656,7 @@ extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const 
                                       const double q[4], int mem, int corr_kind, const double *z2, const double *R2,
                                       int r_kind2, const double *quat_meas2, const uint8_t *mask2, int mem2)
 {
-  CALL(c, IMU_STEP | PRED_REFUSE | NEEDS_STATE);
+  CALL(c, IMU_STEP | PRED_TAKE | PRED_WITH_OUT | NEEDS_STATE);
   if (!imu_block || !lo_block || !q || !z2 || !R2 || !quat_meas2) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: NULL input");
   if (corr_kind != PB_CORR_POS_ORIENT && corr_kind != PB_CORR_POS_YAW) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: bad corr_kind %d", corr_kind);
   if (mem2 == PB_HOST_BROADCAST && r_kind2 == PB_R_DIAG) r_kind2 = PB_R_DIAG_BROADCAST;
@@ -1963,10 +1968,29 @@ extern "C" int pb_smooth_log_slots(int n_steps, int stride)
 // LegOdoCommon's lin_rate update exactly as the per-message path applies them (pb_predict, pb_update_indexed).  Same slots, sink order
 // and head afterwards.  On an error the head goes back to the context's own array (the pre-call head, or the newest posterior once
 // the forward pass is over) and no output / predicted slot is left pending.
+// corr (pb_smooth_log_corrected; NULL or no ticks: none): a step with a tick takes the tick's correction behind its pair, in both
+// passes -- fused as pb_step_legodo_correct does (pbk_step_correct, which also takes the predicted slot), otherwise as one more
+// pb_update_indexed_orient into the step's filtered slot.  "Filtered" is then the posterior of the step's LAST measurement.
 static int smooth_log_impl(pb_ctx *c, const char *who, bool fused, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
-                           const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms)
+                           const uint8_t *mask_stream, const double q[4], double dt, int first_slot, pb_smooth_sink sink, void *user, float *elapsed_ms,
+                           const pb_corr_stream *corr = nullptr)
 {
   if (n_steps < 1 || stride < 1 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "%s: bad argument", who);
+  const int n_ticks = corr ? corr->n_ticks : 0;
+  int m2 = 0, r_kind2 = PB_R_DIAG;
+  const int *idx2 = nullptr;
+  if (n_ticks != 0) {
+    static const int idx_po[6] = { 9, 10, 11, 6, 7, 8 }, idx_py[4] = { 9, 10, 11, 8 };
+    if (corr->kind != PB_CORR_POS_ORIENT && corr->kind != PB_CORR_POS_YAW) return fail(c, PB_ERR_ARG, "%s: bad correction kind %d", who, corr->kind);
+    m2 = (corr->kind == PB_CORR_POS_ORIENT) ? 6 : 4;
+    idx2 = (corr->kind == PB_CORR_POS_ORIENT) ? idx_po : idx_py;
+    r_kind2 = corr->r_kind2;
+    if (n_ticks < 0 || !corr->step || !corr->z2 || !corr->R2 || !corr->quat_meas2) return fail(c, PB_ERR_ARG, "%s: correction stream: NULL input", who);
+    if (r_kind2 != PB_R_DIAG && r_kind2 != PB_R_DIAG_BROADCAST) return fail(c, PB_ERR_ARG, "%s: R2 must be diagonal (PB_R_DIAG or PB_R_DIAG_BROADCAST)", who);
+    for (int t = 0; t < n_ticks; t++)
+      if (corr->step[t] < 0 || corr->step[t] >= n_steps || (t > 0 && corr->step[t] <= corr->step[t - 1]))
+        return fail(c, PB_ERR_ARG, "%s: correction steps must be strictly increasing and in [0, %d) (entry %d: %d)", who, n_steps, t, corr->step[t]);
+  }
   const int K = stride, T = n_steps, M = (T + K - 1) / K, need = pb_smooth_log_slots(T, K);
   if (first_slot < 0 || first_slot + need > c->nhist)
     return fail(c, PB_ERR_STATE, "%s: needs checkpoint slots [%d, %d), %d are reserved (pb_history_reserve)", who, first_slot, first_slot + need, c->nhist);
@@ -1988,10 +2012,25 @@ static int smooth_log_impl(pb_ctx *c, const char *who, bool fused, int n_steps, 
   auto step = [&](int j, int pred_slot, int filt_slot) -> int {
     const double *imu = imu_stream + (size_t) j * 7 * B, *lo = lo_stream + (size_t) j * 6 * B;
     const uint8_t *mask = mask_stream ? mask_stream + (size_t) j * B : nullptr;
+    // this step's correction tick, if it has one
+    const double *z2 = nullptr, *R2 = nullptr, *qm2 = nullptr;
+    const uint8_t *mask2 = nullptr;
+    if (n_ticks > 0) {
+      const int32_t *at = std::lower_bound(corr->step, corr->step + n_ticks, (int32_t) j);
+      if (at != corr->step + n_ticks && *at == j) {
+        const size_t t = (size_t) (at - corr->step);
+        z2 = corr->z2 + t * m2 * B;
+        R2 = (r_kind2 == PB_R_DIAG) ? corr->R2 + t * m2 * B : corr->R2;
+        qm2 = corr->quat_meas2 + t * 4 * B;
+        mask2 = corr->mask2 ? corr->mask2 + t * B : nullptr;
+      }
+    }
     if (fused) {
       c->pred_slot = pred_slot;
       c->out_slot = filt_slot;
-      const int r = pbk_step(c, true, imu, lo, mask, q);
+      const int r = z2 ? pbk_step_correct(c, corr->kind, imu, lo, mask, q, z2, r_kind2 == PB_R_DIAG ? R2 : nullptr,
+                                          r_kind2 == PB_R_DIAG ? nullptr : R2, qm2, mask2)
+                       : pbk_step(c, true, imu, lo, mask, q);
       c->pred_slot = -1;
       return r;
     }
@@ -1999,7 +2038,10 @@ static int smooth_log_impl(pb_ctx *c, const char *who, bool fused, int n_steps, 
     int rc = pbk_step(c, false, imu, nullptr, nullptr, q);
     if (rc) return rc;
     c->out_slot = filt_slot;
-    return update_common(c, 3, idx_v, lo, lo + 3 * B, PB_R_DIAG, nullptr, false, mask, PB_DEVICE);
+    rc = update_common(c, 3, idx_v, lo, lo + 3 * B, PB_R_DIAG, nullptr, false, mask, PB_DEVICE);
+    if (rc || !z2) return rc;
+    c->out_slot = filt_slot;   // the correction lands where the pair's posterior is
+    return update_common(c, m2, idx2, z2, R2, r_kind2, qm2, true, mask2, PB_DEVICE);
   };
   int rc = timed_begin(c, elapsed_ms);
   if (rc || (rc = detach_head(c, true))) return bail(rc);
@@ -2050,6 +2092,17 @@ extern "C" int pb_smooth_log_fused(pb_ctx *c, int n_steps, int stride, const dou
   // (ahead of the argument checks: also a call that is refused for its arguments or slots leaves the head in the context's own array)
   if (int rc = detach_head(c, true)) return rc;
   return smooth_log_impl(c, "pb_smooth_log_fused", true, n_steps, stride, imu_stream, lo_stream, mask_stream, q, dt, first_slot, sink, user, elapsed_ms);
+}
+
+extern "C" int pb_smooth_log_corrected(pb_ctx *c, int n_steps, int stride, const double *imu_stream, const double *lo_stream,
+                                       const uint8_t *mask_stream, const double q[4], double dt, int first_slot, const pb_corr_stream *corr,
+                                       int fused, pb_smooth_sink sink, void *user, float *elapsed_ms)
+{
+  CALL(c, PRED_FORGET | NEEDS_STATE);
+  // (ahead of the argument checks, as pb_smooth_log_fused: a refused call too leaves the head in the context's own array)
+  if (int rc = detach_head(c, true)) return rc;
+  return smooth_log_impl(c, "pb_smooth_log_corrected", fused != 0, n_steps, stride, imu_stream, lo_stream, mask_stream, q, dt, first_slot, sink, user,
+                         elapsed_ms, corr);
 }
 
 static int calib_copy_impl(pb_ctx *c, int reps, float *elapsed_ms, uint64_t *checksum)

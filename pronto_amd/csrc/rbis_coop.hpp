@@ -196,7 +196,7 @@ template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, bool LE
 PB_HD void coop_role_core(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k,
                           const CorrInputs &cin_ = CorrInputs(), SP sp = SP())
 {
-  static_assert(!SP::on || (PREDICT && UPDATE && CORR::M == 0 && !LEG && SIX == 0), "the predicted rows: the plain fused step only");
+  static_assert(!SP::on || (PREDICT && UPDATE && !LEG && SIX == 0), "the predicted rows: the fused step, with or without a CORR stage");
   static_assert(!LEG || (UPDATE && PREDICT), "the odometry wave feeds a predict + update step");
   static_assert(SIX == 0 || (UPDATE && PREDICT), "the six-row leg-odometry modes ride on a predict + velocity update");
   static_assert(SIX != 2 || (CORR::M == 3 && !CORR::ORIENT), "SIX == 2: the second block is a 3-row vector block of role C's states");
@@ -543,7 +543,7 @@ template <int NS, bool UPDATE, class CORR = NoCorr, bool PREDICT = true, int SIX
 PB_HD void coop_role_passive_x(LD ld, ST st, XW xw, XR xr, SYNC sync, const StepInputs &in, const Consts &k,
                                const CorrInputs &cin = CorrInputs(), const SixIn &six = SixIn(), SP sp = SP())
 {
-  static_assert(!SP::on || (PREDICT && UPDATE && CORR::M == 0 && SIX == 0), "the predicted rows: the plain fused step only");
+  static_assert(!SP::on || (PREDICT && UPDATE && SIX == 0), "the predicted rows: the fused step, with or without a CORR stage");
   static_assert(SIX != 1 || (UPDATE && PREDICT && CORR::M == 0), "SIX == 1 rides on a predict + velocity update");
   using L = Lay<NS>;
   using C = Coop<NS>;

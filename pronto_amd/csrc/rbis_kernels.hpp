@@ -761,6 +761,87 @@ __global__ __launch_bounds__(128, 1) void k_step_coop_pred(const double *st, dou
   }
 }
 
+// k_step_coop<15, true, MH, CORR> (the fused step with a correction stage: pb_step_legodo_correct) that also writes the PREDICTED
+// posterior into `pred`, as k_step_coop_pred does for the plain fused step: each role stores its rows of the INS posterior the moment
+// its predict is final and goes on into the leg-odometry update and the correction.  Same inputs, same input order, the same
+// arithmetic for the filtered posterior, bit for bit.  15 states only: with 21 the correction stage alone already spills (pb_step.hip).
+template <int NS, int MH, class CORR>
+__global__ __launch_bounds__(128, 1) void k_step_coop_corr_pred(const double *st, double *sto, double *pred, int B,
+                                                                const double *__restrict__ imu, const double *__restrict__ lo,
+                                                                const uint8_t *__restrict__ mask, double qg, double qa,
+                                                                double qbg, double qba, Consts k, CorrArgs ca, StepBcast bc)
+{
+  static_assert(NS == 15 && CORR::M > 0, "the 15-state fused step with a correction stage");
+  __shared__ double xch[CoopX<NS, CORR>::NXCH][64];
+  const int role = __builtin_amdgcn_readfirstlane((int) (threadIdx.x >> 6));
+  const unsigned wgi = xcd_workgroup(k);   // (half tiles: as k_step_coop)
+  const unsigned tile = k.half_tiles ? (wgi >> 1) : wgi;
+  const unsigned lane = k.half_tiles ? ((threadIdx.x & 31u) | ((wgi & 1u) << 5)) : (threadIdx.x & 63u);
+  const unsigned b = tile * 64u + lane;
+  const unsigned bo = b * 8u, B8 = (unsigned) B * 8u;
+  using IO = TileIO<NS, MemHint<MH>::LA, MemHint<MH>::SA, true>;
+  IO io(st, sto, tile, lane);
+  IO po(pred, pred, tile, lane);   // (only its stores are used)
+  const rsrc_t ri = mkbuf(imu, 7u * B8);
+  const rsrc_t rl = mkbuf(lo, 6u * B8);
+  StepInputs in;
+  if (bc.on & 1) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.gyro[i] = bc.imu[i]; in.accel[i] = bc.imu[3 + i]; }
+    in.dt = bc.imu[6];
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.gyro[i] = ldg(ri, i * B8, bo); in.accel[i] = ldg(ri, (3 + i) * B8, bo); }
+    in.dt = ldg(ri, 6u * B8, bo);
+  }
+  if (bc.on & 2) {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.z[i] = bc.lo[i]; in.rd[i] = bc.lo[3 + i]; }
+  } else {
+#pragma unroll
+    for (int i = 0; i < 3; i++) { in.z[i] = ldg(rl, i * B8, bo); in.rd[i] = ldg(rl, (3 + i) * B8, bo); }
+  }
+  in.upd = (b < (unsigned) B) && (mask == nullptr || mask[b] != 0);
+  in.qg = qg; in.qa = qa; in.qbg = qbg; in.qba = qba;
+  if (k.qblk != nullptr) {
+    const rsrc_t rq = mkbuf(k.qblk, 4u * B8);
+    in.qg = ldg(rq, 0u, bo); in.qa = ldg(rq, B8, bo); in.qbg = ldg(rq, 2u * B8, bo); in.qba = ldg(rq, 3u * B8, bo);
+  }
+  CorrInputs cin;   // (as k_step_coop)
+  const rsrc_t rz = mkbuf(ca.z2, (unsigned) CORR::M * B8);
+  const rsrc_t rr = mkbuf(ca.r2, ca.r2 ? (unsigned) CORR::M * B8 : 0u);
+  const rsrc_t rq2 = mkbuf(ca.qm2, CORR::ORIENT ? 4u * B8 : 0u);
+#pragma unroll
+  for (int i = 0; i < CORR::M; i++) {
+    cin.z[i] = ca.zbc ? ca.zb2[i] : ldg(rz, i * B8, bo);
+    cin.rd[i] = ca.r2 ? ldg(rr, i * B8, bo) : ca.rb2[i];
+  }
+  if (ca.rfull != nullptr) {
+    const rsrc_t rf = mkbuf(ca.rfull, (unsigned) (CORR::M * CORR::M) * B8);
+#pragma unroll
+    for (int i = 0; i < CORR::M; i++) {
+      cin.rd[i] = ldg(rf, (unsigned) (i * CORR::M + i) * B8, bo);
+#pragma unroll
+      for (int j = 0; j < i; j++) cin.ro[i * (i - 1) / 2 + j] = ldg(rf, (unsigned) (j * CORR::M + i) * B8, bo);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 4; i++) cin.qm[i] = CORR::ORIENT ? (ca.zbc ? ca.qb2[i] : ldg(rq2, i * B8, bo)) : 0.0;
+  cin.upd = (b < (unsigned) B) && (ca.mask2 == nullptr || ca.mask2[b] != 0);
+  auto ld = [&io](int comp) { return io.ld(comp); };
+  auto stf = [&io](int comp, double v) { io.st(comp, v); };
+  auto sync = []() { __syncthreads(); };
+  auto xrd = [lane](int s) { return xch[s][lane]; };
+  const PredStore<IO> sp{ &po };
+  if (role == 0) {
+    io.template need<0, Slots<NS>::ROW_SPLIT>();
+    coop_role_core<NS, true, CORR, true, false, 0>(ld, stf, [lane](int s, double v) { xch[s][lane] = v; }, xrd, sync, in, k, cin, sp);
+  } else {
+    io.template need<Slots<NS>::ROW_SPLIT, Slots<NS>::NROW>();
+    coop_role_passive<NS, true, CORR, true>(ld, stf, xrd, sync, in, k, cin, sp);
+  }
+}
+
 // The 21-state hot step on FOUR cooperating waves per 64 filters (rbis_quad.hpp): <= 256 registers per role, so two
 // workgroups (8 waves) share a CU and one tile's loads overlap another's arithmetic and stores.  Same inputs, same
 // posterior (to rounding: the c-b coupling enters P_cc as one additive term instead of inside the row operations) and the
