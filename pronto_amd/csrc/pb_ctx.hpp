@@ -1,4 +1,6 @@
-// pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so
+// pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so.  It includes the
+// argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp), never a kernel: each .hip
+// includes the kernel headers it launches from, so every kernel is compiled in one object.
 // (the kernels are instantiated in fifteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
 // pb_step_corr_pred.hip and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
 // pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip; pb_yawlock.hip;
@@ -11,11 +13,13 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
+#include <vector>
 
 #include "../../include/pronto_batch.h"
-#include "rbis_kernels.hpp"
+#include "rbis_tile_io.hpp"
+#include "rbis_coop.hpp"
 #include "rbis_legodo.hpp"
-#include "rbis_legstep.hpp"
 #include "rbis_jointfilt.hpp"
 #include "rbis_yawlock.hpp"
 
@@ -148,8 +152,18 @@ inline void update_done(pb_ctx *c, double *target)
   c->out_slot = -1;
 }
 
-
 #define LAUNCHCHK(c) HIPCHK((c), hipGetLastError())
+
+// the cache policy of the state round trip (MemHint, chosen in pb_create from the state size) as a compile-time constant: f(MH)
+template <class F>
+static void with_mem_hint(int mem_hint, F f)
+{
+  switch (mem_hint) {
+  case MH_STORE_SC1: f(std::integral_constant<int, MH_STORE_SC1>()); break;
+  case MH_STREAM_NT: f(std::integral_constant<int, MH_STREAM_NT>()); break;
+  default: f(std::integral_constant<int, MH_DEFAULT>()); break;
+  }
+}
 
 // in front of the ONE step launch of a call that was given a mask (pb_set_imu_valid): the IMU block with the samples of the filters
 // WITHOUT a message replaced by what reproduces their angular-velocity / acceleration entries (pronto_batch.hip); the block itself

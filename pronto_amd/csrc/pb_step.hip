@@ -1,18 +1,7 @@
-// pb_step.hip -- launchers of the step kernels (k_step, k_step_coop, k_replay_fused); see pb_ctx.hpp.
-#include <type_traits>
-
+// pb_step.hip -- launchers of the step kernels (k_step, k_step_coop, k_step_quad) and of the replay kernels; see pb_ctx.hpp.
 #include "pb_ctx.hpp"
-
-// the cache policy of the state round trip (MemHint, chosen in pb_create from the state size) as a compile-time constant: f(MH)
-template <class F>
-static void with_mem_hint(int mem_hint, F f)
-{
-  switch (mem_hint) {
-  case MH_STORE_SC1: f(std::integral_constant<int, MH_STORE_SC1>()); break;
-  case MH_STREAM_NT: f(std::integral_constant<int, MH_STREAM_NT>()); break;
-  default: f(std::integral_constant<int, MH_DEFAULT>()); break;
-  }
-}
+#include "rbis_step_kernels.hpp"
+#include "rbis_replay_kernels.hpp"
 
 // The ONE launch of the step kernel this context runs: from `st` into `out`, a grid that covers nb filters (the inputs stay blocks
 // [rows][B] of the whole batch: the kernels take B as the row stride).  half: two workgroups per tile -- the whole-batch 15-state

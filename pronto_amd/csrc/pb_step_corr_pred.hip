@@ -2,6 +2,7 @@
 // pb_step_legodo_correct): k_step_coop_corr_pred, one object of its own so that the step kernels' objects (pb_step.hip,
 // pb_step_pred.hip) stay what they were.
 #include "pb_ctx.hpp"
+#include "rbis_step_kernels.hpp"
 
 template <int MH, class CORR>
 static void launch_corr_pred(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
@@ -23,9 +24,7 @@ static int launch_corr_pred_mh(pb_ctx *c, int corr_kind, double *out, double *pr
 int pbk_step_corr_pred_kernel(pb_ctx *c, int corr_kind, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask,
                               const double q[4], const CorrArgs &ca, const StepBcast &bc)
 {
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: return launch_corr_pred_mh<MH_STORE_SC1>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc);
-  case MH_STREAM_NT: return launch_corr_pred_mh<MH_STREAM_NT>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc);
-  default: return launch_corr_pred_mh<MH_DEFAULT>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc);
-  }
+  int rc = -1;
+  with_mem_hint(c->mem_hint, [&](auto mh) { rc = launch_corr_pred_mh<decltype(mh)::value>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc); });
+  return rc;
 }

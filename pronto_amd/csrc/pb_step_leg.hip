@@ -2,6 +2,7 @@
 // Built as two objects (-DPB_LEG_NS=15 | 21: k_step_leg | k_step_quad_leg) so that `make -j` compiles them side by side;
 // each holds the three measurement modes (SIX = 0 lin_rate, 1 lin_rot_rate, 2 pos_and_lin_rate) x the three cache policies.
 #include "pb_ctx.hpp"
+#include "rbis_legstep.hpp"
 
 #ifndef PB_LEG_NS
 #error "PB_LEG_NS = 15 | 21"
@@ -27,11 +28,7 @@ template <int SIX>
 static void launch_step_leg_mh(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin,
                                const LegStepArgs &la)
 {
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: launch_step_leg<MH_STORE_SC1, SIX>(c, out, imu, q, bc, lin, la); break;
-  case MH_STREAM_NT: launch_step_leg<MH_STREAM_NT, SIX>(c, out, imu, q, bc, lin, la); break;
-  default: launch_step_leg<MH_DEFAULT, SIX>(c, out, imu, q, bc, lin, la); break;
-  }
+  with_mem_hint(c->mem_hint, [&](auto mh) { launch_step_leg<decltype(mh)::value, SIX>(c, out, imu, q, bc, lin, la); });
 }
 
 #if PB_LEG_NS == 15

@@ -1,6 +1,7 @@
 // pb_step_pred.hip -- the fused step that also keeps its prediction (pb_set_pred_slot): k_step_coop_pred / k_step_quad_pred, one object of its own so
 // that the step kernels' object (pb_step.hip) stays what it was.
 #include "pb_ctx.hpp"
+#include "rbis_step_kernels.hpp"
 
 template <int MH>
 static int launch_pred_mh(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
@@ -27,9 +28,7 @@ static int launch_pred_mh(pb_ctx *c, double *out, double *pred, const double *im
 int pbk_step_pred_kernel(pb_ctx *c, double *out, double *pred, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                          const StepBcast &bc)
 {
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: return launch_pred_mh<MH_STORE_SC1>(c, out, pred, imu, lo, mask, q, bc);
-  case MH_STREAM_NT: return launch_pred_mh<MH_STREAM_NT>(c, out, pred, imu, lo, mask, q, bc);
-  default: return launch_pred_mh<MH_DEFAULT>(c, out, pred, imu, lo, mask, q, bc);
-  }
+  int rc = -1;
+  with_mem_hint(c->mem_hint, [&](auto mh) { rc = launch_pred_mh<decltype(mh)::value>(c, out, pred, imu, lo, mask, q, bc); });
+  return rc;
 }

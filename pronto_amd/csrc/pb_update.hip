@@ -2,6 +2,7 @@
 // (one lane, the filter in registers) for m <= 4, k_update_coop_rt<M, MH> (two waves per tile, rbis_quad_rt.hpp) for m = 5, 6
 // where the one-lane kernel spills; 21 states: pb_update_rt21.hip.  See pb_ctx.hpp.
 #include "pb_ctx.hpp"
+#include "rbis_update_kernels.hpp"
 #include "rbis_quad_rt.hpp"
 
 template <int NS, int M, int MH>
@@ -34,11 +35,7 @@ static void launch_update_m(pb_ctx *c, const int *idx, const double *z, const do
     ia.v[i] = idx[i];
     da.v[i] = rb ? rb[i] : 0.0;
   }
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: launch_update_mh<NS, M, MH_STORE_SC1>(c, ia, da, z, R, rkind, qm, mask); break;
-  case MH_STREAM_NT: launch_update_mh<NS, M, MH_STREAM_NT>(c, ia, da, z, R, rkind, qm, mask); break;
-  default: launch_update_mh<NS, M, MH_DEFAULT>(c, ia, da, z, R, rkind, qm, mask); break;
-  }
+  with_mem_hint(c->mem_hint, [&](auto mh) { launch_update_mh<NS, M, decltype(mh)::value>(c, ia, da, z, R, rkind, qm, mask); });
 }
 
 template <int NS>

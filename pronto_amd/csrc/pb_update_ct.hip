@@ -4,6 +4,8 @@
 // state, no column gather -- instead of the generic run-time-index kernel k_update.  LegOdoCommon's lin_rot_rate list reaches
 // the pass-through angular-velocity states: 15 states take it on the one-lane in-register kernel k_update_lane.  See pb_ctx.hpp.
 #include "pb_ctx.hpp"
+#include "rbis_step_kernels.hpp"
+#include "rbis_update_kernels.hpp"
 
 template <int NS, int MH, class CORR>
 static void launch_ct(pb_ctx *c, double *out, const CorrArgs &ca)
@@ -15,23 +17,13 @@ template <class CORR>
 static void launch_ct_mh(pb_ctx *c, double *out, const CorrArgs &ca)
 {
   if (c->ns == 15) {
-    switch (c->mem_hint) {
-    case MH_STORE_SC1: launch_ct<15, MH_STORE_SC1, CORR>(c, out, ca); break;
-    case MH_STREAM_NT: launch_ct<15, MH_STREAM_NT, CORR>(c, out, ca); break;
-    default: launch_ct<15, MH_DEFAULT, CORR>(c, out, ca); break;
-    }
+    with_mem_hint(c->mem_hint, [&](auto mh) { launch_ct<15, decltype(mh)::value, CORR>(c, out, ca); });
   } else if (c->quad21) {
-    switch (c->mem_hint) {
-    case MH_STORE_SC1: k_update_quad<CORR, MH_STORE_SC1><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    case MH_STREAM_NT: k_update_quad<CORR, MH_STREAM_NT><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    default: k_update_quad<CORR, MH_DEFAULT><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    }
+    with_mem_hint(c->mem_hint, [&](auto mh) {
+      k_update_quad<CORR, decltype(mh)::value><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, c->k, ca);
+    });
   } else if constexpr (CORR::M <= 4) {  // PRONTO_BATCH_QUAD21=0: the two-role mapping (its six-row variants spill: not built)
-    switch (c->mem_hint) {
-    case MH_STORE_SC1: launch_ct<21, MH_STORE_SC1, CORR>(c, out, ca); break;
-    case MH_STREAM_NT: launch_ct<21, MH_STREAM_NT, CORR>(c, out, ca); break;
-    default: launch_ct<21, MH_DEFAULT, CORR>(c, out, ca); break;
-    }
+    with_mem_hint(c->mem_hint, [&](auto mh) { launch_ct<21, decltype(mh)::value, CORR>(c, out, ca); });
   }
 }
 
@@ -87,11 +79,9 @@ int pbk_update_ct(pb_ctx *c, int m, const int *idx, const double *z, const doubl
   case 8: launch_ct_mh<CorrGpfChiPos>(c, out, ca); break;
   case 9: launch_ct_mh<CorrGpfZ>(c, out, ca); break;
   default:  // a list that reaches the pass-through states: the one-lane in-register kernel (15 states only)
-    switch (c->mem_hint) {
-    case MH_STORE_SC1: k_update_lane<15, 6, IdxVelOmega, MH_STORE_SC1><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    case MH_STREAM_NT: k_update_lane<15, 6, IdxVelOmega, MH_STREAM_NT><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    default: k_update_lane<15, 6, IdxVelOmega, MH_DEFAULT><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->k, ca); break;
-    }
+    with_mem_hint(c->mem_hint, [&](auto mh) {
+      k_update_lane<15, 6, IdxVelOmega, decltype(mh)::value><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->k, ca);
+    });
     break;
   }
   LAUNCHCHK(c);

@@ -234,15 +234,10 @@ __global__ __launch_bounds__(64) void k_step_yawlock(const double *st, double *s
 template <int NS, int MODE>
 void launch_step(pb_ctx *c, double *out, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
 {
-#define PB_YAW_LAUNCH(MH) \
-  k_step_yawlock<NS, MODE, MH><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain, utime, \
-                                                                c->yawd, c->yawi, z_out, quat_out, mask_out, c->k)
-  switch (c->mem_hint) {
-  case MH_STORE_SC1: PB_YAW_LAUNCH(MH_STORE_SC1); break;
-  case MH_STREAM_NT: PB_YAW_LAUNCH(MH_STREAM_NT); break;
-  default: PB_YAW_LAUNCH(MH_DEFAULT); break;
-  }
-#undef PB_YAW_LAUNCH
+  with_mem_hint(c->mem_hint, [&](auto mh) {
+    k_step_yawlock<NS, MODE, decltype(mh)::value><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain,
+                                                                                  utime, c->yawd, c->yawi, z_out, quat_out, mask_out, c->k);
+  });
 }
 
 __global__ void k_yawlock_reset(double *yd, int64_t *yi, long stride, int B)

@@ -1,11 +1,16 @@
 // pronto_batch.hip -- host side of the C ABI declared in include/pronto_batch.h: context, staging, launches.
-// The kernels live in rbis_kernels.hpp, the per-filter arithmetic in rbis_device.hpp.
+// The kernels launched from here are the utility, front-end, stand-alone leg-odometry and joint-filter ones (the four kernel headers
+// below, included by this file only); the step / update / smoother kernels are launched from the pb_*.hip units (pb_ctx.hpp).
+// The per-filter arithmetic is rbis_device.hpp.
 // There is no CPU path here: without a gfx950 device pb_create fails with PB_ERR_NO_DEVICE.
 #include <algorithm>
 #include <new>
 
 #include "pb_ctx.hpp"
+#include "rbis_util_kernels.hpp"
 #include "rbis_frontend.hpp"
+#include "rbis_legodo_kernels.hpp"
+#include "rbis_jointfilt_kernels.hpp"
 
 #define PB_VERSION_STR "pronto_batch 0.3 gfx950"
 
@@ -58,7 +63,7 @@ extern "C" int pb_create(pb_ctx **out, int n_states, int batch, int device, int 
     // 162 -> 146 us).  PRONTO_BATCH_XCD=0/1 forces it either way for A/B runs.
     const char *e = getenv("PRONTO_BATCH_XCD");
     c->k.xcd_remap = e ? (e[0] == '1') : 1;
-    // Cache policy of the state round trip (rbis_kernels.hpp MemHint), measured on both step kernels: a state that
+    // Cache policy of the state round trip (rbis_tile_io.hpp MemHint), measured on both step kernels: a state that
     // fits the XCDs' L2s (< ~48 MB) wants the default policy (sc1 stores 7 % slower at 32k x 15 states); up to ~1.3x
     // the 256 MB memory-side cache sc1 stores are 1-4 % faster; beyond, non-temporal loads+stores are 7-15 % faster
     // (1M filters: 469 -> 417 us) and 10-40 % SLOWER if used on a cache-sized state.  PRONTO_BATCH_MEMHINT=0/1/2 forces.

@@ -13,7 +13,7 @@
 
 #include <stdint.h>
 
-#include "rbis_kernels.hpp"
+#include "rbis_tile_io.hpp"
 
 namespace pb {
 

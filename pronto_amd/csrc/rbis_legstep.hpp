@@ -16,24 +16,13 @@
 // inputs (a float joint block, or nothing for a broadcast message) and removes the 49-byte measurement block.
 #pragma once
 
-#include "rbis_kernels.hpp"
+#include "rbis_tile_io.hpp"
 #include "rbis_legodo.hpp"
 #include "rbis_quad.hpp"
 
 namespace pb {
 
 #if defined(__HIPCC__)
-struct LegStepArgs {
-  double *legd;
-  int64_t *legi;
-  long stride;
-  int64_t utime;
-  double r2, r2_uncertain;
-  double *lo_out;     // [6][B] or NULL: the measurement, kept for a later re-application of this update (history replay)
-  uint8_t *mask_out;  // [B] (with lo_out)
-  LegMeasPar mp;      // SIX != 0: the six-row modes' variances; lo_out [12][B], mask_out [2][B] as pb_legodo_set_measurement_mode
-};
-
 // The odometry wave's measurement for the step roles, shared by the two pair kernels.  SIX == 0: lin_rate.  SIX == 1 / 2:
 // LegOdoCommon's lin_rot_rate / pos_and_lin_rate (leg_measurement6) split into the velocity block (zv, rv, valid_v) and the
 // other block (z2, r2, on2): mode 2's per-filter fall-back to lin_rate is the velocity block alone.
@@ -276,7 +265,7 @@ __global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, doub
   const unsigned bo = b * 8u, B8 = (unsigned) B * 8u;
   TileIO<21, MemHint<MH>::LA, MemHint<MH>::SA> io(st, sto, tile, lane);
   // (each role requests its inputs inside its own branch: hoisted above the role switch they cost the four-wave kernel its
-  // registers -- 428 bytes of scratch here, as rbis_kernels.hpp k_step_quad found before)
+  // registers -- 428 bytes of scratch here, as rbis_step_kernels.hpp k_step_quad found before)
   auto inputs = [&]() {
     const rsrc_t ri = mkbuf(imu, 7u * B8);
     StepInputs in;

@@ -20,7 +20,8 @@
 // One generic role body, instantiated per wave with its row range: ownership is a constexpr predicate on the component.
 #pragma once
 
-#include "rbis_kernels.hpp"
+#include "rbis_tile_io.hpp"
+#include "rbis_quad.hpp"
 
 namespace pb {
 
@@ -63,7 +64,7 @@ __device__ __forceinline__ void quad_rt_pick(int idxk, IO &io, XW &&xw)
   if constexpr (I < NS) {
     if (idxk == I) {
       // (a distinct marker per branch keeps the compiler from merging the bodies into one that reads through a selected
-      // address, which would pin the wave's rows in scratch memory: rbis_kernels.hpp pick_column)
+      // address, which would pin the wave's rows in scratch memory: rbis_update_kernels.hpp pick_column)
       asm volatile("; wave %0 column %1 -> %2" ::"n"(W), "n"(I), "n"(KK));
       static_for<NS>([&](auto JJ) {
         constexpr int j = decltype(JJ)::value;

@@ -25,13 +25,13 @@
 #include <hip/hip_runtime.h>
 
 #include "rbis_device.hpp"
-#include "rbis_kernels.hpp"
+#include "rbis_tile_io.hpp"
 #include "rbis_lds_stream.hpp"
 #include "rbis_smooth_lane.hpp"
 
 namespace pb {
 
-// cache-policy bits of the row loads / stores (rbis_kernels.hpp: 1 = sc0, 2 = nt, 16 = sc1).  Every checkpoint is read once and the
+// cache-policy bits of the row loads / stores (rbis_tile_io.hpp: 1 = sc0, 2 = nt, 16 = sc1).  Every checkpoint is read once and the
 // posterior written once: non-temporal both ways, 85.7 us against 87.4-88.5 at 64k filters (loads only: 90.4, stores only: 86.7,
 // nt loads + sc1 stores: 87.9), no worse at 4k-128k filters and in pb_smooth_log
 #ifndef SMW_LOAD_AUX

@@ -1,4 +1,4 @@
-"""Static guard of the 16-byte-store hazard workaround (rbis_kernels.hpp stg2): in a hipcc -S dump, no
+"""Static guard of the 16-byte-store hazard workaround (rbis_tile_io.hpp stg2): in a hipcc -S dump, no
 instruction may write a data register of a `buffer_store_dwordx4` before the `s_nop` that follows the store.
     hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o step.s pronto_amd/csrc/pb_step.hip
     python scripts/chk_store_hazard.py step.s         (exit code 1 on a violation; tests/test_isa_hazard.py runs it)"""

@@ -1,7 +1,7 @@
 // host_harness.cpp -- TEST-ONLY: compiles pronto_amd/csrc/rbis_device.hpp (the per-lane arithmetic the HIP kernels
 // run) with g++ so that `-m "not gpu"` tests can check that arithmetic against the oracle in a container without
 // a GPU.  It is NOT part of the product: libpronto_batch.so contains no host path and pronto_amd/ never loads this.
-// The glue below mirrors k_step / k_update in rbis_kernels.hpp.
+// The glue below mirrors k_step (rbis_step_kernels.hpp) / k_update_lane (rbis_update_kernels.hpp).
 #include <cstdint>
 #include <cstring>
 

@@ -212,7 +212,7 @@ def test_measurement_covariances_from_1e_minus_12_to_1e_plus_6(pa, oracle, n, fu
 def test_store_hazard_regression_thousands_of_launches(pa, n):
     """a buffer_store_dwordx4 with an SGPR soffset directly followed by a VALU write of one of its data registers
     stored the NEW value in 16 lanes of the row about once per 1000 launches, until every 16-byte store got an `s_nop 1` tied
-    to its data registers (rbis_kernels.hpp stg2).  The guard: 5 000 launches of the hot step kernel (k_step_coop<15> /
+    to its data registers (rbis_tile_io.hpp stg2).  The guard: 5 000 launches of the hot step kernel (k_step_coop<15> /
     k_step_quad for 21 states) plus 1 000 of the tile copy (k_calib_copy) on 64k filters; the same 50-step replay must give
     the same bits -- every 64-bit word of the 73 / 135 MB state -- 100 times over (pb_state_checksum).
     (scripts/chk_store_hazard.py checks the same property statically on the ISA; tests/test_isa_hazard.py runs it.)"""

@@ -1,5 +1,5 @@
 """Static guard of the 16-byte-store hazard workaround: the ISA hipcc emits for the step kernels must keep every
-`buffer_store_dwordx4`'s data registers untouched until the `s_nop` behind the store (rbis_kernels.hpp stg2).  Runs on the
+`buffer_store_dwordx4`'s data registers untouched until the `s_nop` behind the store (rbis_tile_io.hpp stg2).  Runs on the
 CPU tier (hipcc cross-compiles); the GPU tier repeats thousands of launches and compares bits
 (tests/test_gpu_edge_cases.py::test_store_hazard_regression_thousands_of_launches)."""
 import os

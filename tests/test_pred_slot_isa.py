@@ -1,5 +1,5 @@
 """The predicted-slot step kernels (k_step_coop_pred, k_step_quad_pred: pb_step_pred.hip) on the CPU tier: hipcc's ISA keeps the
-16-byte-store guard (rbis_kernels.hpp stg2: the update overwrites the very registers the predicted rows were just stored from) and
+16-byte-store guard (rbis_tile_io.hpp stg2: the update overwrites the very registers the predicted rows were just stored from) and
 the resource budget of the kernel each one extends:
   k_step_coop_pred<15>  two waves per SIMD, no AGPRs, no scratch (k_step_coop<15>: the same);
   k_step_quad_pred      two waves per SIMD, no AGPRs, <= 16 bytes of scratch -- the bound tests/test_isa_hazard.py holds k_step_quad
