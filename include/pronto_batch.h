@@ -588,6 +588,97 @@ int pb_smooth_log_corrected(pb_ctx *ctx, int n_steps, int stride, const double *
                             const uint8_t *mask_stream, const double q[4], double dt, int first_slot, const pb_corr_stream *corr,
                             int fused, pb_smooth_sink sink, void *user, float *elapsed_ms);
 
+/* ---- accuracy against ground truth (motion_estimate/scripts/drift_per_distance.py) ------------------------------------------
+ * The reference judges an estimator by comparing POSE_BODY with POSE_GROUND_TRUTH (Vicon): between two ground-truth messages
+ * more than parameterTimeElapsedThreshold apart it compares the RELATIVE motion of the estimate with that of the truth and
+ * publishes pronto::error_metrics_t on PRONTO_ERROR.  Here every filter of the batch keeps the script's State
+ * (the anchor ground-truth pose `last`, the anchor estimate `last_est`) and accumulators next to its filter state, and one kernel
+ * launch per ground-truth message (one lane per filter, about 0.5 KB per filter) replaces the flush + pb_get_head + host loop a
+ * caller needs otherwise.  Scoring reads the filter's position (state rows 9..11) and quaternion and writes nothing of the filter:
+ * head, history and log-likelihood are unchanged bit for bit, and a pending pb_set_output_slot / pb_set_pred_slot stays pending.
+ * Quaternions are w, x, y, z and are not normalised, as in the script (botpy.py:30-88).
+ *
+ * Drift windows (PB_SCORE_DRIFT), per filter with a valid message (drift_per_distance.py:70-138):
+ *   no anchor yet (anchor utime < 0, :79)   last <- (utime, pos, q), last_est <- the filter's estimate; nothing else
+ *   otherwise  dist = |pos - last.pos| (:60); the window closes when (double)(utime - last.utime) > time_threshold_s * 1e6 (the
+ *              script's strict comparison, :65), or when distance_threshold > 0 and dist > distance_threshold (the test the script
+ *              carries commented out, :62-63; 0 = off = the script as it ships)
+ *   on closing gt_ab = inv(last) o (pos, q), se_ab = inv(last_est) o estimate (botpy.transform_relative), and error_metrics_t:
+ *              pos_error = se_ab.t - gt_ab.t, pos_error_norm, rpy_error = [0, 0, yaw(se_ab) - yaw(gt_ab)] in degrees, NOT wrapped
+ *              (:107-109), distance_travelled = dist, percent_ddt = 100 pos_error_norm / dist -- the IEEE quotient: inf or NaN
+ *              when the truth did not move (:104) --, utime = utime, and
+ *              time_elapsed = (last.utime - utime) * 1e-6, which is NEGATIVE: the script subtracts the wrong way round (:131) and
+ *              its sign is kept.  Then last <- (utime, pos, q), last_est <- estimate (:136-137).
+ * Absolute error (PB_SCORE_ABS; an addition, the script has none): at every valid message, whatever the order of the messages,
+ * e = estimate.pos - pos and the yaw difference wrapped into (-180, 180] degrees.  It is the supported way to score smoothed
+ * posteriors (an explicit `slot`), whose newest-first order gives other drift windows.
+ */
+enum pb_score_flags { PB_SCORE_DRIFT = 1, PB_SCORE_ABS = 2 };
+/* rows of the per-filter score state, doubles (pb_score_get rows_out) */
+enum pb_score_row {
+  PB_SCORE_ANCHOR_GT = 0,             /* 7 rows: `last` pos[3], orientation[4] (w, x, y, z)                                  */
+  PB_SCORE_ANCHOR_EST = 7,            /* 7 rows: `last_est` pos[3], orientation[4]                                           */
+  PB_SCORE_LAST_POS_ERROR = 14,       /* the newest window's error_metrics_t, in the message's field order (10 rows):        */
+  PB_SCORE_LAST_POS_ERROR_NORM = 17,  /*   pos_error[3], pos_error_norm [m],                                                 */
+  PB_SCORE_LAST_RPY_ERROR = 18,       /*   rpy_error[3] [deg] (roll and pitch always 0, yaw not wrapped),                    */
+  PB_SCORE_LAST_DISTANCE = 21,        /*   distance_travelled [m],                                                           */
+  PB_SCORE_LAST_PERCENT_DDT = 22,     /*   percent_ddt (non-finite when distance_travelled = 0),                             */
+  PB_SCORE_LAST_TIME_ELAPSED = 23,    /*   time_elapsed [s], NEGATIVE (the script's sign)                                    */
+  PB_SCORE_SUM_ERR = 24,              /* sum of pos_error_norm over the closed windows                                       */
+  PB_SCORE_SUM_ERR_SQ = 25,           /* sum of pos_error_norm^2                                                             */
+  PB_SCORE_MAX_ERR = 26,              /* largest pos_error_norm                                                              */
+  PB_SCORE_SUM_DISTANCE = 27,         /* sum of distance_travelled                                                           */
+  PB_SCORE_SUM_TIME = 28,             /* sum of |time_elapsed|                                                               */
+  PB_SCORE_SUM_YAW_SQ = 29,           /* sum of (rpy_error[2] wrapped into (-180, 180])^2                                    */
+  PB_SCORE_SUM_PDDT = 30,             /* sum of percent_ddt over the windows with distance_travelled > 0 (PB_SCORE_N_DDT)    */
+  PB_SCORE_MAX_PDDT = 31,             /* largest percent_ddt of those windows                                                */
+  PB_SCORE_ABS_SUM_SQ = 32,           /* PB_SCORE_ABS: sum of |estimate.pos - pos|^2                                         */
+  PB_SCORE_ABS_MAX = 33,              /* PB_SCORE_ABS: largest |estimate.pos - pos|                                          */
+  PB_SCORE_ABS_SUM_YAW_SQ = 34,       /* PB_SCORE_ABS: sum of (yaw(estimate) - yaw(truth) wrapped into (-180, 180] deg)^2    */
+  PB_SCORE_ROWS = 35
+};
+/* rows of the per-filter score state, 64-bit integers (pb_score_get counts_out) */
+enum pb_score_count {
+  PB_SCORE_ANCHOR_UTIME = 0,  /* last.utime; -2 = no anchor yet (State.__init__, drift_per_distance.py:31) */
+  PB_SCORE_LAST_UTIME = 1,    /* utime of the newest window's error_metrics_t; -2 = no window yet            */
+  PB_SCORE_N_WINDOWS = 2,     /* closed windows                                                              */
+  PB_SCORE_N_DDT = 3,         /* closed windows with distance_travelled > 0                                  */
+  PB_SCORE_ABS_N = 4,         /* PB_SCORE_ABS messages                                                       */
+  PB_SCORE_COUNTS = 5
+};
+/* what pb_score_best ranks by; a filter with no window (with distance > 0) / no PB_SCORE_ABS message has no data for it */
+enum pb_score_metric {
+  PB_SCORE_MEAN_PDDT = 0,  /* PB_SCORE_SUM_PDDT / PB_SCORE_N_DDT: mean percent drift per distance travelled   */
+  PB_SCORE_RMS_DRIFT = 1,  /* sqrt(PB_SCORE_SUM_ERR_SQ / PB_SCORE_N_WINDOWS) [m]                              */
+  PB_SCORE_ATE_RMSE = 2    /* sqrt(PB_SCORE_ABS_SUM_SQ / PB_SCORE_ABS_N) [m]: absolute trajectory error       */
+};
+/* State.__init__ (drift_per_distance.py:25-40) for every filter: allocates the score state on the first call, clears it on every
+ * call (again = reset).  time_threshold_s: parameterTimeElapsedThreshold (10.0 in the script); distance_threshold:
+ * parameterDDTThreshold (0.25 in the script, unused there), 0 = off.  PB_ERR_ARG: a negative or NaN threshold. */
+int pb_score_init(pb_ctx *ctx, double time_threshold_s, double distance_threshold);
+/* on_pose_gt (drift_per_distance.py:70-138) for every filter, with most_recent_est (on_pose_est, :53-56) = the filter's position and
+ * quaternion as they are in `slot`: PB_SLOT_HEAD = wherever the head lives now (the context's own array, or the checkpoint slot an
+ * update wrote it into), else a checkpoint slot.  pose7 = pos[3], orientation[4]: [7][B] (PB_HOST, PB_DEVICE) or [7] host values for
+ * every filter (PB_HOST_BROADCAST: one robot's truth for a whole sweep; kernel arguments, nothing of batch size is moved).
+ * utimes [B] or NULL: per-filter message times instead of utime; valid [B] or NULL: 0 = this filter has no message, it costs the read
+ * of its byte and nothing else.  Both live where pose7 lives (host for PB_HOST_BROADCAST).  flags: PB_SCORE_DRIFT | PB_SCORE_ABS,
+ * at least one.  One launch on the context's stream; nothing is synchronised beyond the copy of PB_HOST inputs.
+ * PB_ERR_STATE: before pb_reset or pb_score_init, slot out of range.  PB_ERR_ARG: NULL pose7, unknown flags or mem. */
+int pb_score_ground_truth(pb_ctx *ctx, int64_t utime, const int64_t *utimes, const double *pose7, const uint8_t *valid, int slot,
+                          int flags, int mem);
+/* the score state of filters [first, first + count): rows_out [PB_SCORE_ROWS][count] doubles, counts_out [PB_SCORE_COUNTS][count]
+ * 64-bit integers, either may be NULL; mem PB_HOST (synchronises) or PB_DEVICE. */
+int pb_score_get(pb_ctx *ctx, int first, int count, double *rows_out, int64_t *counts_out, int mem);
+/* the newest error_metrics_t of one filter (what the script publishes on PRONTO_ERROR, :124-133), host: *utime (-2: no window yet) and
+ * out[10] in the message's field order: pos_error[3], pos_error_norm, rpy_error[3], distance_travelled, percent_ddt, time_elapsed
+ * (negative, see above).  Synchronises. */
+int pb_score_last(pb_ctx *ctx, int filter, int64_t *utime, double out[10]);
+/* the filter with the smallest `metric` (enum pb_score_metric) among the filters that have data for it, found on the device (two
+ * launches); on a tie the lowest filter index.  A filter whose metric is NaN counts as without data.  No filter with data:
+ * *filter_out = -1 and *value_out = 0.  value_out may be NULL.  Synchronises.  Replaces the log-likelihood ranking a sweep had to
+ * fall back on (examples/param_sweep.c) by the reference's own accuracy measure. */
+int pb_score_best(pb_ctx *ctx, int metric, int *filter_out, double *value_out);
+
 /* ---- estimator queries (mav_state_est.hpp:20-22) -------------------------------------------------------- */
 
 /* MavStateEstimator::getHeadState + getMeasurementsLogLikelihood for filters [first, first+count):

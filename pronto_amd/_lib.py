@@ -18,6 +18,9 @@ PB_HOST, PB_DEVICE, PB_HOST_BROADCAST = 0, 1, 2
 PB_R_DIAG_BROADCAST, PB_R_DIAG, PB_R_FULL = 0, 1, 2
 PB_CORR_POS_ORIENT, PB_CORR_POS_YAW = 0, 1
 PB_SLOT_HEAD = -1
+PB_SCORE_DRIFT, PB_SCORE_ABS = 1, 2
+PB_SCORE_ROWS, PB_SCORE_COUNTS = 35, 5
+PB_SCORE_MEAN_PDDT, PB_SCORE_RMS_DRIFT, PB_SCORE_ATE_RMSE = 0, 1, 2
 
 
 def sources():
@@ -136,6 +139,11 @@ _SIGS = {
     "pb_step_yawlock_joints": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                          C.c_void_p]),
     "pb_yawlock_get": (C.c_int, [C.c_void_p, C.c_int, _dp, C.POINTER(C.c_int64)]),
+    "pb_score_init": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "pb_score_ground_truth": (C.c_int, [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]),
+    "pb_score_get": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "pb_score_last": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), _dp]),
+    "pb_score_best": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), _dp]),
     "pb_imu_notch_init": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "pb_imu_notch": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_history_reserve": (C.c_int, [C.c_void_p, C.c_int]),

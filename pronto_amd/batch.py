@@ -32,7 +32,7 @@ def _ptr(a, dtype=np.float64, shape=None):
         raise ValueError("expected an array of shape %s, got %s" % (tuple(shape), tuple(a.shape)))
     if _is_torch(a):
         import torch
-        want = {np.float64: torch.float64, np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32}[dtype]
+        want = {np.float64: torch.float64, np.uint8: torch.uint8, np.float32: torch.float32, np.int32: torch.int32, np.int64: torch.int64}[dtype]
         if a.dtype != want or not a.is_contiguous():
             raise TypeError("expected a contiguous %s tensor" % want)
         return C.c_void_p(a.data_ptr()), (PB_DEVICE if a.is_cuda else PB_HOST)
@@ -477,6 +477,58 @@ class BatchEstimator:
         self._chk(self._L.pb_yawlock_get(self._h, int(b), poses, info))
         return np.array(poses), dict(counter=int(info[0]), lock_init=int(info[1]), disable_until=int(info[2]), outcome=int(info[3]) & 255,
                                      slips=int(info[3]) >> 8)
+
+    # --- accuracy against ground truth (drift_per_distance.py) ---
+    SCORE_METRICS = {"mean_pddt": _lib.PB_SCORE_MEAN_PDDT, "rms_drift": _lib.PB_SCORE_RMS_DRIFT, "ate_rmse": _lib.PB_SCORE_ATE_RMSE}
+
+    def score_init(self, time_threshold_s=10.0, distance_threshold=0.0):
+        """the script's State for every filter (again = reset); the defaults are the script's"""
+        if not (time_threshold_s >= 0 and distance_threshold >= 0):
+            raise ValueError("score_init: thresholds must be >= 0")
+        self._chk(self._L.pb_score_init(self._h, float(time_threshold_s), float(distance_threshold)))
+
+    def score_ground_truth(self, utime, pose7, valid=None, utimes=None, slot=_lib.PB_SLOT_HEAD, drift=True, absolute=False):
+        """on_pose_gt for every filter.  pose7 = pos[3], orientation[4] (w, x, y, z): [7, B] (numpy or device tensor) or a 1-D numpy
+        array of 7 values, one robot's truth for every filter.  valid [B] uint8 / utimes [B] int64 live where pose7 lives (numpy for
+        the 7-value form)."""
+        flags = (_lib.PB_SCORE_DRIFT if drift else 0) | (_lib.PB_SCORE_ABS if absolute else 0)
+        if not flags:
+            raise ValueError("score_ground_truth: drift and / or absolute")
+        pp, mp = _ptr_block(pose7, 7, self.B)
+        if pp is None:
+            raise ValueError("score_ground_truth: pose7 is required")
+        pv, mv = _ptr(valid, np.uint8, shape=(self.B,))
+        pu, mu = _ptr(utimes, np.int64, shape=(self.B,))
+        _same_mem(PB_HOST if mp == PB_HOST_BROADCAST else mp, mv, mu)
+        self._chk(self._L.pb_score_ground_truth(self._h, int(utime), pu, pp, pv, int(slot), flags, mp))
+
+    def score_get(self, first=0, count=None):
+        """(rows [PB_SCORE_ROWS, count] float64, counts [PB_SCORE_COUNTS, count] int64), host"""
+        count = self.B - first if count is None else count
+        if first < 0 or count < 0 or first + count > self.B:
+            raise ValueError("score_get: range [%d, +%d) outside batch %d" % (first, count, self.B))
+        rows, counts = np.empty((_lib.PB_SCORE_ROWS, count)), np.empty((_lib.PB_SCORE_COUNTS, count), dtype=np.int64)
+        self._chk(self._L.pb_score_get(self._h, int(first), int(count), C.c_void_p(rows.ctypes.data), C.c_void_p(counts.ctypes.data), PB_HOST))
+        return rows, counts
+
+    def score_last(self, b):
+        """the newest error_metrics_t of filter b (utime = -2: no window yet)"""
+        if not 0 <= b < self.B:
+            raise ValueError("score_last: filter %d of %d" % (b, self.B))
+        ut, out = C.c_int64(), (C.c_double * 10)()
+        self._chk(self._L.pb_score_last(self._h, int(b), C.byref(ut), out))
+        o = np.array(out)
+        return dict(utime=ut.value, pos_error=o[0:3], pos_error_norm=o[3], rpy_error=o[4:7], distance_travelled=o[7], percent_ddt=o[8],
+                    time_elapsed=o[9])
+
+    def score_best(self, metric="mean_pddt"):
+        """(filter, value) with the smallest metric among the filters that have data; filter = -1: none has"""
+        m = self.SCORE_METRICS.get(metric, metric)
+        if m not in self.SCORE_METRICS.values():
+            raise ValueError("score_best: metric must be one of %s" % sorted(self.SCORE_METRICS))
+        f, v = C.c_int(), C.c_double()
+        self._chk(self._L.pb_score_best(self._h, int(m), C.byref(f), C.byref(v)))
+        return f.value, v.value
 
     # --- IMU front end ---
     def imu_notch_init(self, notch_freq, fs=1000.0):

@@ -3336,6 +3336,148 @@ private:
   std::vector<int> filters_;
 };
 
+// motion_estimate/scripts/drift_per_distance.py for every filter of the batch: the reference's accuracy evaluation (POSE_BODY against
+// POSE_GROUND_TRUTH, published as pronto::error_metrics_t on PRONTO_ERROR) as a handler on the ground-truth pose channel.  It is not
+// a sensor: processMessage creates no update and nothing enters the history; it scores the device head on the device
+// (pb_score_ground_truth) and leaves the filter as it is.  Wire it as a subscribePose callback of LogPlayer, SegmentBatcher or
+// SegmentStreamer; a filter whose segment has no message (valid = 0) is not touched.  A message it cannot take (pos and
+// orientation in different memory spaces, a PB_DEVICE pose that is not one [7][B] block, a failed call) is dropped with
+// est->last_status set; `valid` is honoured for host messages only, as msgs::pose_t documents it.
+//   thresholds: the script's (parameterTimeElapsedThreshold = 10.0; the distance test off) unless the optional keys
+//   state_estimator.error_metrics.time_elapsed_threshold / .distance_threshold are present
+class DriftPerDistance {
+public:
+  double time_elapsed_threshold = 10.0, distance_threshold = 0.0;
+  bool absolute = true;              // also keep the absolute error (PB_SCORE_ABS; an addition to the script)
+  std::string error_channel = "PRONTO_ERROR";
+  int64_t messages = 0, published = 0;
+  explicit DriftPerDistance(BotParam *param)
+  {
+    auto opt = [&](const char *k, double dflt) {
+      auto it = param->kv.find(k);
+      return it == param->kv.end() ? dflt : atof(it->second.c_str());
+    };
+    time_elapsed_threshold = opt("state_estimator.error_metrics.time_elapsed_threshold", time_elapsed_threshold);
+    distance_threshold = opt("state_estimator.error_metrics.distance_threshold", distance_threshold);
+  }
+  // PRONTO_ERROR events of ONE chosen filter go to `log` whenever that filter closes a window (one small read-back per ground-truth
+  // message; without it processMessage never synchronises)
+  void publish(pronto_wire::LogWriter *log, int filter)
+  {
+    log_ = log;
+    publish_filter_ = filter;
+  }
+  // on_pose_gt (drift_per_distance.py:70-138).  The device head is brought up to date first, exactly as getHeadState does: the shim
+  // may be holding an INS step back to fuse it with the leg odometry, and the score must see what POSE_BODY would have carried.
+  void processMessage(const msgs::pose_t *ground_truth, MavStateEstimator *est)
+  {
+    const int B = est->B;
+    if (!ready_) {
+      const int rc0 = pb_score_init(est->ctx, time_elapsed_threshold, distance_threshold);
+      if (rc0 != PB_OK) {  // (a negative threshold key, or no memory: the message is refused, the estimator goes on)
+        fprintf(stderr, "DriftPerDistance: %s\n", pb_last_error(est->ctx));
+        est->last_status = rc0;
+        return;
+      }
+      ready_ = true;
+    }
+    est->flushPending();
+    const int mem = ground_truth->pos.mem;
+    if (ground_truth->orientation.mem != mem) {
+      fprintf(stderr, "DriftPerDistance: pos and orientation must live in the same memory space\n");
+      est->last_status = PB_ERR_ARG;
+      return;
+    }
+    const double *pose7 = nullptr;
+    if (mem == PB_HOST_BROADCAST) {
+      for (int i = 0; i < 3; i++) one_[i] = ground_truth->pos.p[i];
+      for (int i = 0; i < 4; i++) one_[3 + i] = ground_truth->orientation.p[i];
+      pose7 = one_;
+    } else if (ground_truth->orientation.p == ground_truth->pos.p + (size_t) 3 * B) {
+      pose7 = ground_truth->pos.p;  // already one [7][B] block
+    } else if (mem == PB_HOST) {
+      block_.resize((size_t) 7 * B);
+      memcpy(block_.data(), ground_truth->pos.p, sizeof(double) * 3 * (size_t) B);
+      memcpy(block_.data() + (size_t) 3 * B, ground_truth->orientation.p, sizeof(double) * 4 * (size_t) B);
+      pose7 = block_.data();
+    } else {
+      fprintf(stderr, "DriftPerDistance: a PB_DEVICE pose must be one [7][B] block (pos, then orientation)\n");
+      est->last_status = PB_ERR_ARG;
+      return;
+    }
+    const int flags = PB_SCORE_DRIFT | (absolute ? PB_SCORE_ABS : 0);
+    // msgs::pose_t::valid is a HOST array and belongs to PB_HOST messages; a PB_DEVICE message is scored for every filter
+    const uint8_t *valid = mem == PB_DEVICE ? nullptr : ground_truth->valid;
+    int rc = pb_score_ground_truth(est->ctx, ground_truth->utime, nullptr, pose7, valid, PB_SLOT_HEAD, flags, mem);
+    if (rc != PB_OK) {
+      est->last_status = rc;
+      return;
+    }
+    messages++;
+    if (log_ != nullptr && publish_filter_ >= 0 && publish_filter_ < B) {
+      pronto_wire::error_metrics_t em;
+      if (newest(est, publish_filter_, em) && em.utime != last_published_) {
+        std::vector<uint8_t> buf;
+        em.encode(buf);
+        log_->write(em.utime, error_channel, buf);
+        last_published_ = em.utime;
+        published++;
+      }
+    }
+  }
+  // the newest error_metrics_t of one filter; false: no window has closed yet (or an error, est->last_status)
+  bool newest(MavStateEstimator *est, int filter, pronto_wire::error_metrics_t &em) const
+  {
+    double o[10];
+    int64_t utime = -2;
+    const int rc = pb_score_last(est->ctx, filter, &utime, o);
+    if (rc != PB_OK) {
+      est->last_status = rc;
+      return false;
+    }
+    if (utime < 0) return false;
+    em.utime = utime;
+    for (int i = 0; i < 3; i++) { em.pos_error[i] = o[i]; em.rpy_error[i] = o[4 + i]; }
+    em.pos_error_norm = o[3];
+    em.distance_travelled = o[7];
+    em.percent_ddt = o[8];
+    em.time_elapsed = o[9];
+    return true;
+  }
+  pronto_wire::error_metrics_t metrics(MavStateEstimator *est, int filter) const
+  {
+    pronto_wire::error_metrics_t em;
+    em.utime = -2;
+    newest(est, filter, em);
+    return em;
+  }
+  // the accumulators of filters [first, first + count): rows [PB_SCORE_ROWS][count], counts [PB_SCORE_COUNTS][count] (enum pb_score_row / _count)
+  bool rows(MavStateEstimator *est, int first, int count, std::vector<double> &rows_out, std::vector<int64_t> &counts_out) const
+  {
+    rows_out.assign((size_t) PB_SCORE_ROWS * count, 0.0);
+    counts_out.assign((size_t) PB_SCORE_COUNTS * count, 0);
+    const int rc = pb_score_get(est->ctx, first, count, rows_out.data(), counts_out.data(), PB_HOST);
+    if (rc != PB_OK) est->last_status = rc;
+    return rc == PB_OK;
+  }
+  // the filter with the smallest metric (enum pb_score_metric) and its value; -1: no filter has data
+  int best(MavStateEstimator *est, int metric, double *value = nullptr) const
+  {
+    int f = -1;
+    const int rc = pb_score_best(est->ctx, metric, &f, value);
+    if (rc != PB_OK) est->last_status = rc;
+    return rc == PB_OK ? f : -1;
+  }
+
+private:
+  bool ready_ = false;
+  double one_[7] = { 0, 0, 0, 1, 0, 0, 0 };
+  std::vector<double> block_;
+  pronto_wire::LogWriter *log_ = nullptr;
+  int publish_filter_ = -1;
+  int64_t last_published_ = -2;
+};
+
 // Log replay (lcm_front_end.cpp:223-229 handle loop, reading a recorded segment instead of the network): events are
 // dispatched in file order to the subscribed channels.  One recorded robot feeds EVERY filter of the batch -- the
 // batch differs in parameters / initial state, not in data (param_sweep.py:39-52) -- so a decoded message is handed to

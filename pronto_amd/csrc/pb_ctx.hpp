@@ -1,10 +1,10 @@
 // pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so.  It includes the
-// argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp), never a kernel: each .hip
+// argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp), never a kernel: each .hip
 // includes the kernel headers it launches from, so every kernel is compiled in one object.
-// (the kernels are instantiated in fifteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// (the kernels are instantiated in sixteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
 // pb_step_corr_pred.hip and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
 // pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip; pb_yawlock.hip;
-// pronto_batch.hip the C ABI and the rest).
+// pb_score.hip the ground-truth scorer with its C ABI; pronto_batch.hip the C ABI and the rest).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,6 +22,7 @@
 #include "rbis_legodo.hpp"
 #include "rbis_jointfilt.hpp"
 #include "rbis_yawlock.hpp"
+#include "rbis_score.hpp"
 
 using namespace pb;
 
@@ -74,6 +75,11 @@ struct pb_ctx {
   bool yaw_standing_dev = false, yaw_gyro_dev = false;
   int yaw_standing_all = 0;
   double yaw_gyro_all = 0.0;
+  // drift per distance against ground truth (pb_score_init, rbis_score.hpp): per-filter state [PB_SCORE_ROWS][stride] doubles +
+  // [PB_SCORE_COUNTS][stride] 64-bit words
+  ScorePar score_par;
+  double *scored = nullptr;
+  int64_t *scorei = nullptr;
   double *notch = nullptr;  // IMU notch cascade state [36][stride] (pb_imu_notch_init)
   NotchCoef notch_coef;
   bool notch_ready = false;
@@ -164,6 +170,84 @@ static void with_mem_hint(int mem_hint, F f)
   default: f(std::integral_constant<int, MH_DEFAULT>()); break;
   }
 }
+
+// staging area for PB_HOST inputs/outputs (pronto_batch.hip): a device buffer of at least `bytes`
+int stage_reserve(pb_ctx *c, size_t bytes);
+// Resolve the caller buffers of one call (up to 7: pb_step_legodo_correct): device pointers pass through; host buffers are packed into the staging area.
+struct Part {
+  const void *src;
+  size_t bytes;
+  const void *dev;
+};
+int stage_in(pb_ctx *c, int mem, Part *parts, int n);
+
+// ---- the per-call contract: what an entry point takes from the context, declared in ONE line at its top -- CALL(c, flags) ----
+// The one-shot inputs belong to the NEXT call that takes them, whatever becomes of it: the pb_set_imu_valid mask to the next call that
+// takes an IMU step, the per-filter message times / validity (pb_legodo_set_message_times) to the next odometry or pair call,
+// pb_set_pred_slot to the next pb_step_legodo / pb_step_legodo_split / pb_step_legodo_correct.  The guard takes them FIRST, before anything is validated, so
+// that a call that fails early cannot leave them behind for an unrelated later call, and forgets them when the call returns.
+enum : unsigned {
+  IMU_STEP = 1,      // takes the IMU validity mask: held in imu_valid_cur for the duration of the call (pbk_idle_prepare)
+  LEG_TIMES = 2,     // takes the message times / validity (Call::times)
+  PRED_TAKE = 4,     // writes a predicted posterior: consumes a pending predicted slot, whatever becomes of the call
+  PRED_REFUSE = 8,   // takes an IMU step or an update but writes no predicted posterior: with a slot pending it refuses and forgets it
+  PRED_FORGET = 16,  // runs a whole log of steps with predicted slots of its own: a pending one is forgotten
+  NEEDS_STATE = 32,  // PB_ERR_STATE before pb_reset
+  PRED_WITH_OUT = 64,  // (with PRED_TAKE) a checkpointed step only: a predicted slot without a pending output slot is refused as by PRED_REFUSE
+};
+struct LegMsgTimes {
+  const int64_t *utimes = nullptr;
+  const uint8_t *valid = nullptr;
+};
+struct Call {
+  pb_ctx *const c;
+  const unsigned what;
+  LegMsgTimes times;
+  int rc;
+  Call(pb_ctx *ctx, const char *fn, unsigned flags) : c(ctx), what(flags) { rc = enter(fn); }
+  Call(const Call &) = delete;
+  ~Call()
+  {
+    if (!c) return;
+    if (what & IMU_STEP) c->imu_valid_cur = nullptr;
+    if (what & PRED_TAKE) c->pred_slot = -1;
+  }
+
+ private:
+  int enter(const char *fn)
+  {
+    if (!c) return PB_ERR_ARG;
+    if (what & IMU_STEP) {
+      c->imu_valid_cur = c->imu_valid_next;
+      c->imu_valid_next = nullptr;
+    }
+    if (what & LEG_TIMES) {
+      if (c->leg_ut_on) times.utimes = c->leg_ut_ext ? c->leg_ut_ext : c->leg_ut;
+      if (c->leg_valid_on) times.valid = c->leg_valid_ext ? c->leg_valid_ext : c->leg_valid;
+      c->leg_ut_on = c->leg_valid_on = false;
+      c->leg_ut_ext = nullptr;
+      c->leg_valid_ext = nullptr;
+    }
+    HIPCHK(c, hipSetDevice(c->dev));
+    if ((what & (PRED_REFUSE | PRED_FORGET)) && c->pred_slot >= 0) {
+      c->pred_slot = -1;
+      if (what & PRED_REFUSE)
+        return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / _split / _correct)", fn);
+    }
+    if ((what & PRED_WITH_OUT) && c->pred_slot >= 0 && c->out_slot < 0) {
+      c->pred_slot = -1;
+      return fail(c, PB_ERR_STATE, "%s: no predicted slot here without an output slot (pb_set_output_slot)", fn);
+    }
+    if ((what & NEEDS_STATE) && !c->have_state) return fail(c, PB_ERR_STATE, "%s before pb_reset", fn);
+    // the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
+    if ((what & PRED_TAKE) && c->pred_slot >= 0 && (c->pred_slot >= c->nhist || c->pred_slot == c->out_slot || c->pred_slot == pb_head_slot(c)))
+      return fail(c, PB_ERR_ARG, "predicted slot %d: out of range, the output slot or the head's slot", c->pred_slot);
+    return PB_OK;
+  }
+};
+#define CALL(c, flags)               \
+  Call call((c), __func__, (flags)); \
+  if (call.rc) return call.rc
 
 // in front of the ONE step launch of a call that was given a mask (pb_set_imu_valid): the IMU block with the samples of the filters
 // WITHOUT a message replaced by what reproduces their angular-velocity / acceleration entries (pronto_batch.hip); the block itself

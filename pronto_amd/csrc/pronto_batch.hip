@@ -170,6 +170,8 @@ extern "C" int pb_destroy(pb_ctx *c)
   if (c->yawi) (void) hipFree(c->yawi);
   if (c->yaw_standing) (void) hipFree(c->yaw_standing);
   if (c->yaw_gyro) (void) hipFree(c->yaw_gyro);
+  if (c->scored) (void) hipFree(c->scored);
+  if (c->scorei) (void) hipFree(c->scorei);
   if (c->jf_ring) (void) hipFree(c->jf_ring);
   if (c->jf_kst) (void) hipFree(c->jf_kst);
   if (c->d_small) (void) hipFree(c->d_small);
@@ -336,7 +338,7 @@ extern "C" int pb_upload_sync(pb_ctx *c)
 }
 
 // staging area for PB_HOST inputs/outputs: a device buffer the host blocks are copied into
-static int stage_reserve(pb_ctx *c, size_t bytes)
+int stage_reserve(pb_ctx *c, size_t bytes)
 {
   if (bytes <= c->stage_bytes) return PB_OK;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -348,13 +350,8 @@ static int stage_reserve(pb_ctx *c, size_t bytes)
   return PB_OK;
 }
 
-// Resolve the caller buffers of one call (up to 7: pb_step_legodo_correct): device pointers pass through; host buffers are packed into the staging area.
-struct Part {
-  const void *src;
-  size_t bytes;
-  const void *dev;
-};
-static int stage_in(pb_ctx *c, int mem, Part *parts, int n)
+// the input resolver (Part, pb_ctx.hpp)
+int stage_in(pb_ctx *c, int mem, Part *parts, int n)
 {
   if (mem == PB_DEVICE) {
     for (int i = 0; i < n; i++) parts[i].dev = parts[i].src;
@@ -416,74 +413,7 @@ static int stage_in(pb_ctx *c, int mem, Part *parts, int n)
   return PB_OK;
 }
 
-// ---- the per-call contract: what an entry point takes from the context, declared in ONE line at its top -- CALL(c, flags) ----
-// The one-shot inputs belong to the NEXT call that takes them, whatever becomes of it: the pb_set_imu_valid mask to the next call that
-// takes an IMU step, the per-filter message times / validity (pb_legodo_set_message_times) to the next odometry or pair call,
-// pb_set_pred_slot to the next pb_step_legodo / pb_step_legodo_split / pb_step_legodo_correct.  The guard takes them FIRST, before anything is validated, so
-// that a call that fails early cannot leave them behind for an unrelated later call, and forgets them when the call returns.
-enum : unsigned {
-  IMU_STEP = 1,      // takes the IMU validity mask: held in imu_valid_cur for the duration of the call (pbk_idle_prepare)
-  LEG_TIMES = 2,     // takes the message times / validity (Call::times)
-  PRED_TAKE = 4,     // writes a predicted posterior: consumes a pending predicted slot, whatever becomes of the call
-  PRED_REFUSE = 8,   // takes an IMU step or an update but writes no predicted posterior: with a slot pending it refuses and forgets it
-  PRED_FORGET = 16,  // runs a whole log of steps with predicted slots of its own: a pending one is forgotten
-  NEEDS_STATE = 32,  // PB_ERR_STATE before pb_reset
-  PRED_WITH_OUT = 64,  // (with PRED_TAKE) a checkpointed step only: a predicted slot without a pending output slot is refused as by PRED_REFUSE
-};
-struct LegMsgTimes {
-  const int64_t *utimes = nullptr;
-  const uint8_t *valid = nullptr;
-};
-struct Call {
-  pb_ctx *const c;
-  const unsigned what;
-  LegMsgTimes times;
-  int rc;
-  Call(pb_ctx *ctx, const char *fn, unsigned flags) : c(ctx), what(flags) { rc = enter(fn); }
-  Call(const Call &) = delete;
-  ~Call()
-  {
-    if (!c) return;
-    if (what & IMU_STEP) c->imu_valid_cur = nullptr;
-    if (what & PRED_TAKE) c->pred_slot = -1;
-  }
-
- private:
-  int enter(const char *fn)
-  {
-    if (!c) return PB_ERR_ARG;
-    if (what & IMU_STEP) {
-      c->imu_valid_cur = c->imu_valid_next;
-      c->imu_valid_next = nullptr;
-    }
-    if (what & LEG_TIMES) {
-      if (c->leg_ut_on) times.utimes = c->leg_ut_ext ? c->leg_ut_ext : c->leg_ut;
-      if (c->leg_valid_on) times.valid = c->leg_valid_ext ? c->leg_valid_ext : c->leg_valid;
-      c->leg_ut_on = c->leg_valid_on = false;
-      c->leg_ut_ext = nullptr;
-      c->leg_valid_ext = nullptr;
-    }
-    HIPCHK(c, hipSetDevice(c->dev));
-    if ((what & (PRED_REFUSE | PRED_FORGET)) && c->pred_slot >= 0) {
-      c->pred_slot = -1;
-      if (what & PRED_REFUSE)
-        return fail(c, PB_ERR_STATE, "%s: no predicted slot here (pb_set_pred_slot is for pb_step_legodo / _split / _correct)", fn);
-    }
-    if ((what & PRED_WITH_OUT) && c->pred_slot >= 0 && c->out_slot < 0) {
-      c->pred_slot = -1;
-      return fail(c, PB_ERR_STATE, "%s: no predicted slot here without an output slot (pb_set_output_slot)", fn);
-    }
-    if ((what & NEEDS_STATE) && !c->have_state) return fail(c, PB_ERR_STATE, "%s before pb_reset", fn);
-    // the pending predicted slot against the slots this call writes / reads (pb_set_output_slot may have come after pb_set_pred_slot)
-    if ((what & PRED_TAKE) && c->pred_slot >= 0 && (c->pred_slot >= c->nhist || c->pred_slot == c->out_slot || c->pred_slot == pb_head_slot(c)))
-      return fail(c, PB_ERR_ARG, "predicted slot %d: out of range, the output slot or the head's slot", c->pred_slot);
-    return PB_OK;
-  }
-};
-#define CALL(c, flags)               \
-  Call call((c), __func__, (flags)); \
-  if (call.rc) return call.rc
-
+// (the per-call contract -- CALL(c, flags) -- is in pb_ctx.hpp)
 
 extern "C" int pb_reset(pb_ctx *c, const double *vec, const double *quat, const double *cov, int broadcast, int mem)
 {

@@ -346,6 +346,57 @@ struct behavior_t {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// pronto::error_metrics_t (pronto_error_metrics_t.lcm): what drift_per_distance.py publishes on PRONTO_ERROR when a window
+// closes (drift_per_distance.py:124-133); DriftPerDistance::publish writes it.  Fixed-size.  time_elapsed carries the script's
+// sign: (anchor utime - utime) 1e-6, negative.
+// ---------------------------------------------------------------------------------------------------------------
+struct error_metrics_t {
+  int64_t utime = 0;
+  double pos_error[3] = { 0, 0, 0 };
+  double pos_error_norm = 0;
+  double rpy_error[3] = { 0, 0, 0 };
+  double distance_travelled = 0, percent_ddt = 0, time_elapsed = 0;
+  static const std::vector<Member> &members()
+  {
+    static const std::vector<Member> m = { { "utime", "int64_t", {} },
+                                           { "pos_error", "double", { { LCM_CONST, "3" } } },
+                                           { "pos_error_norm", "double", {} },
+                                           { "rpy_error", "double", { { LCM_CONST, "3" } } },
+                                           { "distance_travelled", "double", {} },
+                                           { "percent_ddt", "double", {} },
+                                           { "time_elapsed", "double", {} } };
+    return m;
+  }
+  static uint64_t fingerprint() { static const uint64_t f = lcm_fingerprint(members()); return f; }
+  void encode(std::vector<uint8_t> &out) const
+  {
+    Writer w;
+    w.u64(fingerprint());
+    w.i64(utime);
+    w.f64s(pos_error, 3);
+    w.f64(pos_error_norm);
+    w.f64s(rpy_error, 3);
+    w.f64(distance_travelled);
+    w.f64(percent_ddt);
+    w.f64(time_elapsed);
+    out.swap(w.buf);
+  }
+  int decode(const void *data, size_t len)
+  {
+    Reader r(data, len);
+    if (r.u64() != fingerprint()) return r.ok ? WIRE_ERR_FINGERPRINT : WIRE_ERR_SHORT;
+    utime = r.i64();
+    r.f64s(pos_error, 3);
+    pos_error_norm = r.f64();
+    r.f64s(rpy_error, 3);
+    distance_travelled = r.f64();
+    percent_ddt = r.f64();
+    time_elapsed = r.f64();
+    return r.ok ? (int) r.pos : WIRE_ERR_SHORT;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // LCM event log
 // ---------------------------------------------------------------------------------------------------------------
 struct LogEvent {
