@@ -1,14 +1,18 @@
-// pb_ctx.hpp -- the context behind the C ABI and the launchers shared by the translation units of libpronto_batch.so.  It includes the
+// pb_ctx.hpp -- the context behind the C ABI, the owner of its device memory (dev_alloc / dev_release) and what crosses the translation
+// units of libpronto_batch.so: the per-call guard, the input resolver and the launchers.  It includes the
 // argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp), never a kernel: each .hip
 // includes the kernel headers it launches from, so every kernel is compiled in one object.
-// (the kernels are instantiated in sixteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// (the kernels are instantiated in nineteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
 // pb_step_corr_pred.hip and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
-// pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip; pb_yawlock.hip;
-// pb_score.hip the ground-truth scorer with its C ABI; pronto_batch.hip the C ABI and the rest).
+// pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
+// and entry points of the C ABI share one unit: pb_legodo.hip leg odometry and joint filters, pb_yawlock.hip, pb_frontend.hip the IMU
+// front end, pb_score.hip the ground-truth scorer; pb_history.hip the checkpoint slots and whole-log smoothing, which launches through
+// pbk_* only; pronto_batch.hip the context, staging, steps, updates and read-back).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -86,7 +90,7 @@ struct pb_ctx {
   // IMU front end per filter (pb_ins_body_block, rbis_frontend.hpp): last body-frame sample [6][stride], previous message time [stride]
   double *ins_last = nullptr;
   int64_t *ins_prev_ut = nullptr;
-  const uint8_t *imu_valid_next = nullptr;   // pb_set_imu_valid: one-shot, taken by the next call that takes an IMU step (Call, pronto_batch.hip) ...
+  const uint8_t *imu_valid_next = nullptr;   // pb_set_imu_valid: one-shot, taken by the next call that takes an IMU step (Call) ...
   const uint8_t *imu_valid_cur = nullptr;    // ... and held here for the duration of that call
   double *imu_keep = nullptr;                // [7][stride]: the IMU block that call's step kernel reads instead (pbk_idle_prepare)
   // chunked uploads (pb_upload_async): fences recorded on the main stream, one event for "the uploads issued so far"
@@ -118,6 +122,7 @@ struct pb_ctx {
   bool smooth_wide_attr = false;
   int n_cu = 256;            // compute units of the device (grid of the persistent smoother kernel)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  std::vector<void *> owned;  // every device allocation behind the pointers above (dev_alloc / dev_release); pb_destroy frees these
   char err[512] = { 0 };
 };
 
@@ -141,6 +146,42 @@ inline int fail(pb_ctx *c, int code, const char *fmt, ...)
 
 inline int nblk(int n) { return (n + 63) / 64; }
 
+// ---- the context's device memory: one owner ----
+// Every device buffer a pb_ctx member points to is allocated here and recorded in c->owned, which pb_destroy frees; no family keeps a
+// free list of its own.  `count` elements of T (bytes for a void pointer); nothing happens when p is set already.
+template <class T>
+hipError_t dev_alloc_hip(pb_ctx *c, T *&p, size_t count)
+{
+  if (p) return hipSuccess;
+  void *mem = nullptr;
+  hipError_t e = hipMalloc(&mem, sizeof(std::conditional_t<std::is_void_v<T>, char, T>) * count);
+  if (e != hipSuccess) return e;
+  c->owned.push_back(mem);
+  p = (T *) mem;
+  return hipSuccess;
+}
+template <class T>
+int dev_alloc(pb_ctx *c, T *&p, size_t count)
+{
+  hipError_t e = dev_alloc_hip(c, p, count);
+  return e == hipSuccess ? PB_OK : fail(c, PB_ERR_HIP, "hipMalloc failed: %s", hipGetErrorString(e));
+}
+// a buffer that is re-made: freed and forgotten, p = NULL (the caller has made sure that nothing in flight still uses it).  Only what
+// the context owns is freed: a pointer that dev_alloc did not record is dropped, not passed to the runtime.
+template <class T>
+hipError_t dev_release(pb_ctx *c, T *&p)
+{
+  const auto at = std::find(c->owned.begin(), c->owned.end(), (void *) p);
+  p = nullptr;
+  if (at == c->owned.end()) return hipSuccess;
+  void *mem = *at;
+  c->owned.erase(at);
+  return hipFree(mem);
+}
+
+// checkpoint slot `slot` of pb_history_reserve
+inline double *slot_ptr(const pb_ctx *c, int slot) { return c->hist + (size_t) slot * c->state_doubles; }
+
 // Where an update writes its posterior.  Normally in place.  With pb_set_output_slot the posterior goes straight into a
 // checkpoint slot (a checkpoint per update without a copy: the step moves the same bytes either way).  If the head IS a
 // checkpoint slot and no output slot was named, the update writes back into the context's own array, so a saved
@@ -149,7 +190,7 @@ int detach_head(pb_ctx *c, bool keep_contents);
 
 inline double *update_target(pb_ctx *c)
 {
-  if (c->out_slot >= 0) return c->hist + (size_t) c->out_slot * c->state_doubles;
+  if (c->out_slot >= 0) return slot_ptr(c, c->out_slot);
   return (c->st != c->st_base) ? c->st_base : c->st;
 }
 inline void update_done(pb_ctx *c, double *target)
@@ -170,6 +211,13 @@ static void with_mem_hint(int mem_hint, F f)
   default: f(std::integral_constant<int, MH_DEFAULT>()); break;
   }
 }
+// the state size as a compile-time constant: f(NS), for the launches that differ in nothing else
+template <class F>
+static void with_ns(int ns, F f)
+{
+  if (ns == 15) f(std::integral_constant<int, 15>());
+  else f(std::integral_constant<int, 21>());
+}
 
 // staging area for PB_HOST inputs/outputs (pronto_batch.hip): a device buffer of at least `bytes`
 int stage_reserve(pb_ctx *c, size_t bytes);
@@ -180,6 +228,30 @@ struct Part {
   const void *dev;
 };
 int stage_in(pb_ctx *c, int mem, Part *parts, int n);
+// The IMU block of a call, resolved into p[0] (with the n - 1 parts behind it that live in the same space) or, PB_HOST_BROADCAST, into
+// bc (pronto_batch.hip)
+int imu_in(pb_ctx *c, const double *imu_block, int imu_mem, StepBcast &bc, Part *p, int n = 1);
+// the joint-state inputs of one message as the kernels take them (LegIn kind 1; pb_legodo.hip)
+int leg_in_joints(pb_ctx *c, const char *who, int n_rows, const float *jpos, const float *jeff, const float *forces, int mem, LegIn &in);
+// the frame of a timed entry point: device time between the two events (elapsed_ms NULL: not timed, no event)
+int timed_begin(pb_ctx *c, const float *elapsed_ms);
+int timed_end(pb_ctx *c, float *elapsed_ms);
+
+// Small read-back of one filter's handler state: `launch(dp, di)` leaves up to 16 doubles and 4 info words in the staging area
+template <class Launch>
+static int get_small(pb_ctx *c, double *d_out, int n_d, int64_t info[4], Launch launch)
+{
+  int rc = stage_reserve(c, 256);
+  if (rc) return rc;
+  double *dp = (double *) c->stage;
+  int64_t *di = (int64_t *) (dp + 16);
+  rc = launch(dp, di);
+  if (rc) return rc;
+  HIPCHK(c, hipMemcpyAsync(d_out, dp, sizeof(double) * n_d, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipMemcpyAsync(info, di, sizeof(int64_t) * 4, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return PB_OK;
+}
 
 // ---- the per-call contract: what an entry point takes from the context, declared in ONE line at its top -- CALL(c, flags) ----
 // The one-shot inputs belong to the NEXT call that takes them, whatever becomes of it: the pb_set_imu_valid mask to the next call that
@@ -250,7 +322,7 @@ struct Call {
   if (call.rc) return call.rc
 
 // in front of the ONE step launch of a call that was given a mask (pb_set_imu_valid): the IMU block with the samples of the filters
-// WITHOUT a message replaced by what reproduces their angular-velocity / acceleration entries (pronto_batch.hip); the block itself
+// WITHOUT a message replaced by what reproduces their angular-velocity / acceleration entries (pb_frontend.hip); the block itself
 // when there is no mask
 const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out);
 
@@ -305,9 +377,7 @@ int pbk_smooth_step(pb_ctx *c, const double *next_pred, const double *next_sm, c
 int pbk_smooth_wide(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);   // 15 states (pb_smooth_wide.hip)
 // pb_select.hip: dst <- src for the filters whose mask_dev entry (device, [B]; non-zero counts as 1) equals `when`, every other column untouched
 int pbk_slot_select(pb_ctx *c, double *dst, const double *src, const uint8_t *mask_dev, int when);
-// pb_yawlock.hip: the yaw-lock handler (rbis_yawlock.hpp).  form: state machine + measurement block + masks; step: the same and the
-// update applied in the one kernel (honours pb_set_output_slot).  z_out [2][B], quat_out [4][B], mask_out [2][B] device or NULL (step)
-int pbk_yawlock_reset(pb_ctx *c);
-int pbk_yawlock_get(pb_ctx *c, int filter, double *poses_dev, int64_t *info_dev);
-int pbk_yawlock_form(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out);
-int pbk_step_yawlock(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out);
+// pronto_batch.hip: the stand-alone indexed (+ orientation, orient) update of pb_update_indexed*, on the kernel the index list and R allow;
+// honours pb_set_output_slot
+int pbk_update_common(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *qm, bool orient,
+                      const uint8_t *mask, int mem);

@@ -12,8 +12,8 @@ extern "C" int pb_score_init(pb_ctx *c, double time_threshold_s, double distance
   CALL(c, 0);
   if (!(time_threshold_s >= 0.0) || !(distance_threshold >= 0.0))
     return fail(c, PB_ERR_ARG, "pb_score_init: thresholds must be >= 0 (time %g s, distance %g m)", time_threshold_s, distance_threshold);
-  if (!c->scored) HIPCHK(c, hipMalloc((void **) &c->scored, sizeof(double) * PB_SCORE_ROWS * (size_t) c->stride));
-  if (!c->scorei) HIPCHK(c, hipMalloc((void **) &c->scorei, sizeof(int64_t) * PB_SCORE_COUNTS * (size_t) c->stride));
+  if (int rc = dev_alloc(c, c->scored, PB_SCORE_ROWS * (size_t) c->stride)) return rc;
+  if (int rc = dev_alloc(c, c->scorei, PB_SCORE_COUNTS * (size_t) c->stride)) return rc;
   c->score_par.time_threshold_s = time_threshold_s;
   c->score_par.distance_threshold = distance_threshold;
   k_score_reset<<<nblk((int) c->stride), 64, 0, c->stream>>>(c->scored, c->scorei, c->stride);
@@ -47,9 +47,10 @@ extern "C" int pb_score_ground_truth(pb_ctx *c, int64_t utime, const int64_t *ut
   gt.utimes = (const int64_t *) p[1].dev;
   gt.valid = (const uint8_t *) p[2].dev;
   // the array the estimate is read from: where the head lives now (as pb_slot_select resolves PB_SLOT_HEAD), or a checkpoint slot
-  const double *st = slot == PB_SLOT_HEAD ? c->st : c->hist + (size_t) slot * c->state_doubles;
-  if (c->ns == 15) k_score_gt<15><<<nblk(c->B), 64, 0, c->stream>>>(st, c->B, c->stride, c->score_par, flags, gt, c->scored, c->scorei);
-  else k_score_gt<21><<<nblk(c->B), 64, 0, c->stream>>>(st, c->B, c->stride, c->score_par, flags, gt, c->scored, c->scorei);
+  const double *st = slot == PB_SLOT_HEAD ? c->st : slot_ptr(c, slot);
+  with_ns(c->ns, [&](auto NS) {
+    k_score_gt<decltype(NS)::value><<<nblk(c->B), 64, 0, c->stream>>>(st, c->B, c->stride, c->score_par, flags, gt, c->scored, c->scorei);
+  });
   LAUNCHCHK(c);
   return PB_OK;
 }

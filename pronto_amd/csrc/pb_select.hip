@@ -50,8 +50,7 @@ __global__ __launch_bounds__(64) void k_slot_select(double *__restrict__ dst, co
 int pbk_slot_select(pb_ctx *c, double *dst, const double *src, const uint8_t *mask_dev, int when)
 {
   const dim3 grid((unsigned) nblk(c->B), (unsigned) (((c->ns == 15 ? Slots<15>::NROW : Slots<21>::NROW) + SEL_ROWS - 1) / SEL_ROWS));
-  if (c->ns == 15) k_slot_select<15><<<grid, 64, 0, c->stream>>>(dst, src, mask_dev, c->B, when);
-  else k_slot_select<21><<<grid, 64, 0, c->stream>>>(dst, src, mask_dev, c->B, when);
+  with_ns(c->ns, [&](auto NS) { k_slot_select<decltype(NS)::value><<<grid, 64, 0, c->stream>>>(dst, src, mask_dev, c->B, when); });
   LAUNCHCHK(c);
   return PB_OK;
 }

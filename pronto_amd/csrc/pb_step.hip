@@ -64,7 +64,7 @@ int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t
 // behind it.  Either way the filtered posterior is the fused step's, bit for bit, and the slot holds what pb_predict would leave.
 static int step_pred(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bc)
 {
-  double *pred = c->hist + (size_t) c->pred_slot * c->state_doubles;
+  double *pred = slot_ptr(c, c->pred_slot);
   const int ps = c->pred_slot;
   c->pred_slot = -1;
   int rc = PB_OK;
@@ -117,7 +117,7 @@ int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, cons
 {
   SlotOut so;
   if (slot0 >= 0) {
-    so.base = c->hist + (size_t) slot0 * c->state_doubles;
+    so.base = slot_ptr(c, slot0);
     so.stride = c->state_doubles;
   }
   // PRONTO_BATCH_REPLAY_ONELANE=1: the first, one-lane-per-filter version (15 states only; A/B runs)
@@ -176,7 +176,7 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
   }
   const StepBcast bc = bcast ? *bcast : StepBcast();
   // a predicted slot pending (pb_set_pred_slot, consumed here): the kernel that also stores the INS posterior (pb_step_corr_pred.hip)
-  double *pred = c->pred_slot >= 0 ? c->hist + (size_t) c->pred_slot * c->state_doubles : nullptr;
+  double *pred = c->pred_slot >= 0 ? slot_ptr(c, c->pred_slot) : nullptr;
   c->pred_slot = -1;
   double *out = update_target(c);
   int rc = PB_OK;

@@ -1,4 +1,5 @@
-// pb_yawlock.hip -- the yaw-lock kernels (rbis_yawlock.hpp) and their launchers.  See pb_ctx.hpp.
+// pb_yawlock.hip -- the yaw-lock handler (rbis_yawlock.hpp): the kernels, their launchers and the pb_yawlock_* / pb_step_yawlock_joints
+// entry points of the C ABI.  See pb_ctx.hpp.
 //   k_yawlock_form      one lane per filter: the handler's state machine, the measurement block and the two masks
 //   k_step_yawlock      the same, and the m <= 2 update applied in the same launch
 //
@@ -260,33 +261,33 @@ __global__ void k_yawlock_get(const double *yd, const int64_t *yi, long stride, 
 
 }  // namespace
 
-int pbk_yawlock_reset(pb_ctx *c)
+// ---- launchers.  form: state machine + measurement block + masks; step: the same and the update applied in the one kernel (honours
+// pb_set_output_slot).  z_out [2][B], quat_out [4][B], mask_out [2][B] device or NULL (step) ----
+static int pbk_yawlock_reset(pb_ctx *c)
 {
   k_yawlock_reset<<<nblk(c->B), 64, 0, c->stream>>>(c->yawd, c->yawi, c->stride, c->B);
   LAUNCHCHK(c);
   return PB_OK;
 }
 
-int pbk_yawlock_get(pb_ctx *c, int filter, double *poses_dev, int64_t *info_dev)
+static int pbk_yawlock_get(pb_ctx *c, int filter, double *poses_dev, int64_t *info_dev)
 {
   k_yawlock_get<<<1, 1, 0, c->stream>>>(c->yawd, c->yawi, c->stride, filter, poses_dev, info_dev);
   LAUNCHCHK(c);
   return PB_OK;
 }
 
-int pbk_yawlock_form(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
+static int pbk_yawlock_form(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
 {
-  if (c->ns == 15)
-    k_yawlock_form<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain, utime, c->yawd, c->yawi,
-                                                          z_out, quat_out, mask_out);
-  else
-    k_yawlock_form<21><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain, utime, c->yawd, c->yawi,
-                                                          z_out, quat_out, mask_out);
+  with_ns(c->ns, [&](auto NS) {
+    k_yawlock_form<decltype(NS)::value><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain, utime, c->yawd,
+                                                                           c->yawi, z_out, quat_out, mask_out);
+  });
   LAUNCHCHK(c);
   return PB_OK;
 }
 
-int pbk_step_yawlock(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
+static int pbk_step_yawlock(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
 {
   double *out = update_target(c);
   if (c->ns == 15) launch_step<15, YL_YAW>(c, out, yin, lin, utime, z_out, quat_out, mask_out);
@@ -296,4 +297,105 @@ int pbk_step_yawlock(pb_ctx *c, const YawIn &yin, const LegIn &lin, int64_t utim
   LAUNCHCHK(c);
   update_done(c, out);
   return PB_OK;
+}
+
+// ---- the entry points of the C ABI ----
+extern "C" int pb_yawlock_init(pb_ctx *c, int mode, int correction_period, int yaw_slip_detect, double yaw_slip_threshold_degrees,
+                               double yaw_slip_disable_period_s, double r_yaw_bias_deg, double r_yaw_deg)
+{
+  if (!c) return PB_ERR_ARG;
+  // (the argument checks come before anything that needs the device)
+  if (mode < YL_YAWBIAS || mode > YL_YAWBIAS_YAW) return fail(c, PB_ERR_ARG, "pb_yawlock_init: mode must be 0 (yawbias), 1 (yaw) or 2 (yawbias_yaw)");
+  if (mode != YL_YAW && c->ns != 21) return fail(c, PB_ERR_ARG, "pb_yawlock_init: mode %d measures the gyro bias (state 17), this context has %d states", mode, c->ns);
+  if (correction_period < 1) return fail(c, PB_ERR_ARG, "pb_yawlock_init: correction_period must be >= 1");
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int rc = dev_alloc(c, c->yawd, NYD * (size_t) c->stride)) return rc;
+  if (int rc = dev_alloc(c, c->yawi, NYI * (size_t) c->stride)) return rc;
+  YawPar &p = c->yaw_par;
+  p.mode = mode;
+  p.period = correction_period;
+  p.slip_detect = yaw_slip_detect != 0;
+  p.slip_threshold_deg = yaw_slip_threshold_degrees;
+  p.slip_disable_s = yaw_slip_disable_period_s;
+  const double rb = r_yaw_bias_deg * M_PI / 180.0, ry = r_yaw_deg * M_PI / 180.0;  // bot_to_radians, bot_sq (rbis_yawlock_update.cpp:80,88)
+  p.r_bias = rb * rb;
+  p.r_yaw = ry * ry;
+  c->yaw_standing_dev = c->yaw_gyro_dev = false;
+  c->yaw_standing_all = 0;
+  c->yaw_gyro_all = 0.0;
+  return pbk_yawlock_reset(c);
+}
+
+// What a handler keeps per filter between messages (pb_yawlock_set_standing / _set_gyro): [B] values in a device array of the
+// context's own, allocated once -- or ONE value for every filter (PB_HOST_BROADCAST), which the caller has stored already.
+template <class T>
+static int keep_per_filter(pb_ctx *c, const char *who, T *&dev, bool &dev_on, const T *src, int mem)
+{
+  if (mem == PB_HOST_BROADCAST) {
+    dev_on = false;
+    return PB_OK;
+  }
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "%s: bad mem", who);
+  if (int rc = dev_alloc(c, dev, (size_t) c->stride)) return rc;
+  HIPCHK(c, hipMemcpyAsync(dev, src, sizeof(T) * (size_t) c->B, mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+  if (mem == PB_HOST) HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+  dev_on = true;
+  return PB_OK;
+}
+
+extern "C" int pb_yawlock_set_standing(pb_ctx *c, const uint8_t *standing, int mem)
+{
+  CALL(c, 0);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_standing before pb_yawlock_init");
+  if (!standing) return fail(c, PB_ERR_ARG, "pb_yawlock_set_standing: NULL input");
+  if (mem == PB_HOST_BROADCAST) c->yaw_standing_all = standing[0] != 0;
+  return keep_per_filter(c, "pb_yawlock_set_standing", c->yaw_standing, c->yaw_standing_dev, standing, mem);
+}
+
+extern "C" int pb_yawlock_set_gyro(pb_ctx *c, const double *body_gyro_z, int mem)
+{
+  CALL(c, 0);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_set_gyro before pb_yawlock_init");
+  if (!body_gyro_z) return fail(c, PB_ERR_ARG, "pb_yawlock_set_gyro: NULL input");
+  if (mem == PB_HOST_BROADCAST) c->yaw_gyro_all = body_gyro_z[0];
+  return keep_per_filter(c, "pb_yawlock_set_gyro", c->yaw_gyro, c->yaw_gyro_dev, body_gyro_z, mem);
+}
+
+static int yawlock_impl(pb_ctx *c, const char *who, bool apply, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                        const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "%s before pb_yawlock_init", who);
+  LegIn lin;
+  int rc = leg_in_joints(c, who, n_rows, joint_position, nullptr, nullptr, mem, lin);
+  if (rc) return rc;
+  lin.utimes = utimes;
+  lin.valid = valid;
+  YawIn yin;
+  yin.standing = c->yaw_standing_dev ? c->yaw_standing : nullptr;
+  yin.gyro_z = c->yaw_gyro_dev ? c->yaw_gyro : nullptr;
+  yin.standing_all = c->yaw_standing_all;
+  yin.gyro_z_all = c->yaw_gyro_all;
+  return apply ? pbk_step_yawlock(c, yin, lin, utime, z_out, quat_out, mask_out) : pbk_yawlock_form(c, yin, lin, utime, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_yawlock_update_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                                        const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  CALL(c, NEEDS_STATE);
+  return yawlock_impl(c, "pb_yawlock_update_joints", false, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_step_yawlock_joints(pb_ctx *c, int64_t utime, const int64_t *utimes, const uint8_t *valid, int n_rows,
+                                      const float *joint_position, int mem, double *z_out, double *quat_out, uint8_t *mask_out)
+{
+  CALL(c, PRED_REFUSE | NEEDS_STATE);
+  return yawlock_impl(c, "pb_step_yawlock_joints", true, utime, utimes, valid, n_rows, joint_position, mem, z_out, quat_out, mask_out);
+}
+
+extern "C" int pb_yawlock_get(pb_ctx *c, int filter, double poses[14], int64_t info[4])
+{
+  CALL(c, 0);
+  if (!c->yawd) return fail(c, PB_ERR_STATE, "pb_yawlock_get before pb_yawlock_init");
+  if (filter < 0 || filter >= c->B || !poses || !info) return fail(c, PB_ERR_ARG, "pb_yawlock_get: bad argument");
+  return get_small(c, poses, 14, info, [&](double *dp, int64_t *di) { return pbk_yawlock_get(c, filter, dp, di); });
 }

@@ -13,13 +13,14 @@ V=${SM_VARIANTS:-$V}   # e.g. SM_VARIANTS="timeline:-DSML_TIMELINE=255" (a tile 
 D=gpurun_scratch/smooth_attr
 if [ "${1:-}" = build ]; then
   mkdir -p $D
-  O=pronto_amd/lib/obj
+  # the library's other objects: the Makefile's own list (print-objs) without the two smoother objects
+  OTHERS=$(make -s -C pronto_amd/csrc print-objs | tr ' ' '\n' | grep -v '/pb_smooth\(_wide\)\?\.o$' | sed 's|^\.\./lib/obj/|pronto_amd/lib/obj/|' | tr '\n' ' ')
+  [ -n "$OTHERS" ] || { echo "no object list from the Makefile (make print-objs)" >&2; exit 1; }
   for v in $V; do
     n=${v%%:*}; fl=$(echo ${v#*:} | tr ',' ' ')
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -DPB_EXPERIMENTS -Ipronto_amd/csrc $fl -c -o $D/pb_smooth_$n.o pronto_amd/csrc/pb_smooth.hip || exit 1
     /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -Wno-unused-function -DPB_EXPERIMENTS -mllvm -disable-machine-licm -Ipronto_amd/csrc $fl -c -o $D/pb_smooth_wide_$n.o pronto_amd/csrc/pb_smooth_wide.hip || exit 1
-    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -shared -o $D/lib_$n.so $O/pronto_batch.o $O/pb_step.o $O/pb_step_pred.o $O/pb_step_leg15.o $O/pb_step_leg21.o $O/pb_update15.o \
-      $O/pb_update21_0.o $O/pb_update21_1.o $O/pb_update21_2.o $O/pb_update_ct.o $O/pb_select.o $O/pb_yawlock.o $O/pb_score.o $D/pb_smooth_$n.o $D/pb_smooth_wide_$n.o || exit 1
+    /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -shared -o $D/lib_$n.so $OTHERS $D/pb_smooth_$n.o $D/pb_smooth_wide_$n.o || exit 1
     rm -f $D/pb_smooth_$n.o $D/pb_smooth_wide_$n.o
   done
   ls $D
