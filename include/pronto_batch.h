@@ -301,6 +301,25 @@ int pb_legodo_set_message_times(pb_ctx *ctx, const int64_t *utimes, const uint8_
  * arguments of the odometry calls).  The pair calls pb_step_legodo_joints / _feet form AND APPLY the same measurement (their
  * lo_block_out / mask_out have the shapes above).  pb_legodo_init puts the mode back to 0. */
 int pb_legodo_set_measurement_mode(pb_ctx *ctx, int mode, double r_xyz, double r_vang, double r_vang_uncertain);
+/* Parameter sweeps over the measurement side of the leg odometry (state-estimator/python/param_sweep.py:39-52, one process per
+ * `-O key=value` there): the eleven state_estimator.legodo.* scalars PER FILTER.  block [PB_LEGPAR_ROWS][B], rows in the .cfg's units:
+ *   PB_LEGPAR_R_VXYZ, _R_VXYZ_UNCERTAIN                       the r_vxyz / r_vxyz_uncertain arguments of every odometry / pair call
+ *   PB_LEGPAR_R_VANG, _R_VANG_UNCERTAIN, _R_XYZ               pb_legodo_set_measurement_mode's
+ *   PB_LEGPAR_SCHMITT_LOW, _HIGH, _LOW_DELAY, _HIGH_DELAY     pb_legodo_init's (delays in us, whole numbers)
+ *   PB_LEGPAR_TOTAL_FORCE, _STANDING_SCHMITT_LEVEL            pb_legodo_set_contact_mode's
+ * The noises are standard deviations, squared where they are used; thresholds, total_force and the level pass through `float` as in
+ * the scalar setters: a block that holds one value per row gives the bits of the scalar calls.  While a block is set its rows replace
+ * those scalars in every pb_legodo_update* and pb_step_legodo_joints / _feet call, and the calls' r_vxyz / r_vxyz_uncertain arguments
+ * are ignored; the flags and modes (filter_contact_events, standing, use_controller_input, the measurement mode) stay per context.
+ * mem = PB_HOST or PB_DEVICE (PB_HOST_BROADCAST: PB_ERR_ARG); either way the block is copied into memory the context owns before the
+ * call returns.  A PB_HOST block is checked per filter -- noises finite and >= 0, high >= low threshold, delays whole numbers in
+ * [0, 2e9] -- and the first offending filter and row are named in pb_last_error (PB_ERR_ARG; the block set before, or none, stays in
+ * force).  A PB_DEVICE BLOCK IS COPIED UNCHECKED: the same rules are the caller's to keep.  block = NULL switches back to the scalars;
+ * so does pb_legodo_init.  PB_ERR_STATE before pb_legodo_init. */
+enum { PB_LEGPAR_R_VXYZ = 0, PB_LEGPAR_R_VXYZ_UNCERTAIN, PB_LEGPAR_R_VANG, PB_LEGPAR_R_VANG_UNCERTAIN, PB_LEGPAR_R_XYZ,
+       PB_LEGPAR_SCHMITT_LOW, PB_LEGPAR_SCHMITT_HIGH, PB_LEGPAR_SCHMITT_LOW_DELAY, PB_LEGPAR_SCHMITT_HIGH_DELAY,
+       PB_LEGPAR_TOTAL_FORCE, PB_LEGPAR_STANDING_SCHMITT_LEVEL, PB_LEGPAR_ROWS };
+int pb_legodo_set_param_block(pb_ctx *ctx, const double *block /* [PB_LEGPAR_ROWS][B] */, int mem);
 /* LegOdoHandler's "ignore the calculated velocity at launch" (state_estimator.legodo.zero_initial_velocity,
  * rbis_legodo_update.cpp:58,264-268), counted PER FILTER on the device: the counter is decremented by every message whose
  * status is valid for that filter (the reference returns NULL before the decrement otherwise, :243-255) and while it stays

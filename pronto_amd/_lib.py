@@ -21,6 +21,9 @@ PB_SLOT_HEAD = -1
 PB_SCORE_DRIFT, PB_SCORE_ABS = 1, 2
 PB_SCORE_ROWS, PB_SCORE_COUNTS = 35, 5
 PB_SCORE_MEAN_PDDT, PB_SCORE_RMS_DRIFT, PB_SCORE_ATE_RMSE = 0, 1, 2
+(PB_LEGPAR_R_VXYZ, PB_LEGPAR_R_VXYZ_UNCERTAIN, PB_LEGPAR_R_VANG, PB_LEGPAR_R_VANG_UNCERTAIN, PB_LEGPAR_R_XYZ, PB_LEGPAR_SCHMITT_LOW,
+ PB_LEGPAR_SCHMITT_HIGH, PB_LEGPAR_SCHMITT_LOW_DELAY, PB_LEGPAR_SCHMITT_HIGH_DELAY, PB_LEGPAR_TOTAL_FORCE,
+ PB_LEGPAR_STANDING_SCHMITT_LEVEL, PB_LEGPAR_ROWS) = range(12)
 
 
 def sources():
@@ -119,6 +122,7 @@ _SIGS = {
     "pb_legodo_update_joints": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
                                           C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p]),
+    "pb_legodo_set_param_block": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int]),
     "pb_legodo_set_zero_initial_velocity": (C.c_int, [C.c_void_p, C.c_int]),
     "pb_legodo_set_message_times": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "pb_legodo_set_measurement_mode": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double]),

@@ -327,6 +327,19 @@ class BatchEstimator:
         self._chk(self._L.pb_legodo_set_measurement_mode(self._h, int(mode), float(r_xyz), float(r_vang), float(r_vang_uncertain)))
         self._leg_mode = int(mode)
 
+    def legodo_set_param_block(self, block):
+        """The odometry's noises and contact thresholds PER FILTER (pb_legodo_set_param_block): block [PB_LEGPAR_ROWS, B] float64 in
+        the .cfg's units, rows _lib.PB_LEGPAR_* -- a numpy array (checked per filter by the library) or a device tensor (copied
+        unchecked); None switches back to the scalars.  The block is copied: the caller's array is free on return."""
+        if block is None:
+            self._chk(self._L.pb_legodo_set_param_block(self._h, None, PB_HOST))
+            return
+        shape = tuple(getattr(block, "shape", ()))
+        if shape != (_lib.PB_LEGPAR_ROWS, self.B):   # (before any call into the library: it takes no lengths)
+            raise ValueError("expected a parameter block of shape %s, got %s" % ((_lib.PB_LEGPAR_ROWS, self.B), shape))
+        p, m = _ptr(block, shape=shape)
+        self._chk(self._L.pb_legodo_set_param_block(self._h, p, m))
+
     def _leg_shapes(self):
         mode = getattr(self, "_leg_mode", 0)
         return ((6, self.B), (self.B,)) if mode == 0 else ((12, self.B), (self.B,) if mode == 1 else (2, self.B))

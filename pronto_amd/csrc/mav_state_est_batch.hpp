@@ -2222,6 +2222,71 @@ public:
     // per update: the measurement block -- z and the diagonal of R, [6][B] (lin_rate) or [12][B] doubles -- and its mask(s) [2][B]
     pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 12 * (size_t) B + 2 * (size_t) B);
     legodo_ready_ = true;
+    sweep_dirty_ = sweep_B_ != 0;   // (pb_legodo_init dropped the block)
+  }
+  // ---- parameter sweeps: the batch's form of the reference's `-O key=value` (state-estimator/python/param_sweep.py:39-52) ----
+  // key: one of the eleven state_estimator.legodo.* names below (with or without that prefix); per_filter: its value for every filter
+  // of the batch, in the .cfg's units.  The rows nobody swept hold the .cfg's value.  The first sweep fixes the batch size the
+  // following ones must have; a wrong key or a wrong length returns false and changes nothing.  Takes effect with the next message
+  // (pb_legodo_set_param_block); a length that is not the estimator's batch size ends the program there like every bad configuration.
+  static const char *sweepKey(int row)
+  {
+    static const char *const keys[PB_LEGPAR_ROWS] = { "r_vxyz", "r_vxyz_uncertain", "r_vang", "r_vang_uncertain", "r_xyz", "schmitt_low_threshold",
+                                                      "schmitt_high_threshold", "schmitt_low_delay", "schmitt_high_delay", "total_force",
+                                                      "standing_schmitt_level" };
+    return keys[row];
+  }
+  bool setSweep(const std::string &key, const std::vector<double> &per_filter)
+  {
+    const std::string prefix = "state_estimator.legodo.";
+    const std::string k = key.compare(0, prefix.size(), prefix) == 0 ? key.substr(prefix.size()) : key;
+    int row = -1;
+    for (int r = 0; r < PB_LEGPAR_ROWS; r++)
+      if (k == sweepKey(r)) row = r;
+    if (row < 0 || per_filter.empty() || (sweep_B_ != 0 && per_filter.size() != sweep_B_)) return false;
+    sweep_B_ = per_filter.size();
+    sweep_rows_[row] = per_filter;
+    sweep_dirty_ = true;
+    return true;
+  }
+  size_t sweep_B_ = 0;
+  std::vector<double> sweep_rows_[PB_LEGPAR_ROWS];
+  bool sweep_dirty_ = false;
+  void applySweep(MavStateEstimator *est)
+  {
+    const size_t B = (size_t) est->B;
+    if (sweep_B_ != B) {
+      fprintf(stderr, "LegOdoHandler: setSweep was given %zu values per key, the batch has %zu filters\n", sweep_B_, B);
+      exit(1);
+    }
+    const LegOdoCommon *lc = leg_odo_common_;
+    auto cfg = [&](int row) -> double {
+      switch (row) {
+      case PB_LEGPAR_R_VXYZ: return lc->R_legodo_vxyz_;
+      case PB_LEGPAR_R_VXYZ_UNCERTAIN: return lc->R_legodo_vxyz_uncertain_;
+      case PB_LEGPAR_R_VANG: return lc->R_legodo_vang_;
+      case PB_LEGPAR_R_VANG_UNCERTAIN: return lc->R_legodo_vang_uncertain_;
+      case PB_LEGPAR_R_XYZ: return lc->R_legodo_xyz_;
+      default: break;
+      }
+      const std::string key = std::string("state_estimator.legodo.") + sweepKey(row);
+      if (row == PB_LEGPAR_TOTAL_FORCE || row == PB_LEGPAR_STANDING_SCHMITT_LEVEL) {  // read only with a robot model (initLegEstimate)
+        const auto it = param_->kv.find(key);
+        return (model_ != nullptr && it != param_->kv.end()) ? atof(it->second.c_str()) : 0.0;
+      }
+      const double v = bot_param_get_double_or_fail(param_, key.c_str());
+      return (row == PB_LEGPAR_SCHMITT_LOW_DELAY || row == PB_LEGPAR_SCHMITT_HIGH_DELAY) ? (double) (int64_t) v : v;
+    };
+    std::vector<double> block((size_t) PB_LEGPAR_ROWS * B);
+    for (int row = 0; row < PB_LEGPAR_ROWS; row++) {
+      if (sweep_rows_[row].empty()) std::fill(block.begin() + (size_t) row * B, block.begin() + (size_t) (row + 1) * B, cfg(row));
+      else std::copy(sweep_rows_[row].begin(), sweep_rows_[row].end(), block.begin() + (size_t) row * B);
+    }
+    if (pb_legodo_set_param_block(est->ctx, block.data(), PB_HOST) != PB_OK) {
+      fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
+      exit(1);
+    }
+    sweep_dirty_ = false;
   }
   // fksolver_->JntToCart looks joints up by name (leg_estimate.cpp:432-436): resolve the chain's names against the message's
   void initChain(const msgs::joint_state_t *msg, MavStateEstimator *est)
@@ -2342,6 +2407,7 @@ public:
     if (ahead != nullptr && ahead->imu_block.mem == PB_HOST && lm->mem == PB_HOST) ahead = nullptr;  // one host staging area
     if (ahead == nullptr) est->flushPending();
     if (!legodo_ready_) initLegEstimate(est);
+    if (sweep_dirty_) applySweep(est);
     if (control_contacts_dirty_) {
       if (pb_legodo_set_control_contacts(est->ctx, n_control_contacts_, PB_HOST_BROADCAST) != PB_OK) fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
       control_contacts_dirty_ = false;
@@ -2431,6 +2497,7 @@ public:
       exit(1);
     }
     if (!legodo_ready_) initLegEstimate(est);
+    if (sweep_dirty_) applySweep(est);
     if (!chain_ready_ || msg->joint_name != chain_names_) initChain(msg, est);
     const float *forces = foot_force_dev_ ? foot_force_dev_ : foot_force_.data();
     int fmem = foot_force_dev_ ? PB_DEVICE : foot_force_mem_;

@@ -2,8 +2,8 @@
 // units of libpronto_batch.so: the per-call guard, the input resolver and the launchers.  It includes the
 // argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp), never a kernel: each .hip
 // includes the kernel headers it launches from, so every kernel is compiled in one object.
-// (the kernels are instantiated in nineteen objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
-// pb_step_corr_pred.hip and pb_step_leg.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
+// (the kernels are instantiated in twenty-one objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// pb_step_corr_pred.hip, pb_step_leg.hip and pb_legpar.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
 // pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
 // and entry points of the C ABI share one unit: pb_legodo.hip leg odometry and joint filters, pb_yawlock.hip, pb_frontend.hip the IMU
 // front end, pb_score.hip the ground-truth scorer; pb_history.hip the checkpoint slots and whole-log smoothing, which launches through
@@ -52,6 +52,8 @@ struct pb_ctx {
   bool leg_ut_on = false, leg_valid_on = false;
   const int64_t *leg_ut_ext = nullptr;    // PB_DEVICE times / validity are read in place: the caller's arrays, not copies
   const uint8_t *leg_valid_ext = nullptr;
+  double *leg_blk = nullptr;      // pb_legodo_set_param_block: the odometry's noises and contact thresholds per filter, [PB_LEGPAR_ROWS][stride]
+  bool leg_blk_on = false;        // ... in force: the kernels read it instead of leg_par.alt / total_force / level and the calls' noises
   LegMeasPar leg_meas;            // pb_legodo_set_measurement_mode: which of LegOdoCommon's measurements the odometry calls write
   LegChain *leg_chain = nullptr;  // forward-kinematics chain table (pb_legodo_set_chain), device copy ...
   LegChain leg_chain_h;           // ... and the host copy (PB_HOST_BROADCAST joint states are reduced to chain angles on the host)
@@ -340,6 +342,9 @@ int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const dou
 // pb_step_leg.hip, one object per state size: the pair kernels' launchers
 int pbk_step_leg15(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin, const LegStepArgs &la);
 int pbk_step_leg21(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin, const LegStepArgs &la);
+// pb_legpar.hip, one object per state size: their siblings that read the context's per-filter parameter block (c->leg_blk)
+int pbk_legpar15(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin, const LegStepArgs &la);
+int pbk_legpar21(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin, const LegStepArgs &la);
 // slot0 >= 0: write-through -- the posterior of step t also goes to checkpoint slot slot0 + t (pb_replay_legodo_checkpointed)
 int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, const uint8_t *mask, const double q[4], int slot0 = -1);
 // pb_step_pred.hip: the fused step that also writes its predicted posterior into `pred` (k_step_coop_pred); -1 = this context has no

@@ -1,6 +1,8 @@
 // pb_legodo.hip -- stand-alone leg odometry, forward kinematics and the joint-position filters in front of them (rbis_legodo.hpp,
 // rbis_jointfilt.hpp): the kernels (rbis_legodo_kernels.hpp, rbis_jointfilt_kernels.hpp), their launches and the pb_legodo_* /
 // pb_joint_filter* / pb_step_legodo_joints / _feet entry points of the C ABI.  See pb_ctx.hpp.
+#include <cmath>
+
 #include "pb_ctx.hpp"
 #include "rbis_legodo_kernels.hpp"
 #include "rbis_jointfilt_kernels.hpp"
@@ -19,6 +21,7 @@ extern "C" int pb_legodo_init(pb_ctx *c, double lt, double ht, int64_t low_delay
   c->leg_meas = LegMeasPar{};
   c->leg_nc_h[0] = c->leg_nc_h[1] = -1;
   c->leg_nc_dev = false;
+  c->leg_blk_on = false;   // (the buffer stays the context's)
   c->leg_par.alt = SchmittPar{ (double) (float) lt, (double) (float) ht, low_delay, high_delay };
   c->leg_par.filter_contact_events = filter_contact_events ? 1 : 0;
   k_legodo_reset<<<nblk(c->B), 64, 0, c->stream>>>(c->legd, c->legi, c->stride, c->B, -1);
@@ -77,6 +80,51 @@ extern "C" int pb_legodo_set_measurement_mode(pb_ctx *c, int mode, double r_xyz,
   c->leg_meas.r_a2 = r_vang * r_vang;
   c->leg_meas.r_a2_uncertain = r_vang_uncertain * r_vang_uncertain;
   if (mode == 2) c->leg_par.world_constraint = 1;        // the position it measures is leg_estimate's world constraint
+  return PB_OK;
+}
+
+static_assert((int) LPR_ROWS == (int) PB_LEGPAR_ROWS && (int) LPR_R_VXYZ == (int) PB_LEGPAR_R_VXYZ && (int) LPR_R_XYZ == (int) PB_LEGPAR_R_XYZ &&
+                  (int) LPR_SCHMITT_LOW == (int) PB_LEGPAR_SCHMITT_LOW && (int) LPR_SCHMITT_HIGH_DELAY == (int) PB_LEGPAR_SCHMITT_HIGH_DELAY &&
+                  (int) LPR_STANDING_SCHMITT_LEVEL == (int) PB_LEGPAR_STANDING_SCHMITT_LEVEL,
+              "rbis_legpar.hpp's rows are the header's");
+
+extern "C" int pb_legodo_set_param_block(pb_ctx *c, const double *block, int mem)
+{
+  CALL(c, 0);
+  if (!c->legd) return fail(c, PB_ERR_STATE, "pb_legodo_set_param_block before pb_legodo_init");
+  if (!block) {  // back to the scalars
+    c->leg_blk_on = false;
+    return PB_OK;
+  }
+  if (mem != PB_HOST && mem != PB_DEVICE) return fail(c, PB_ERR_ARG, "pb_legodo_set_param_block: mem must be PB_HOST or PB_DEVICE");
+  const size_t B = (size_t) c->B;
+  if (mem == PB_HOST) {
+    static const char *const name[PB_LEGPAR_ROWS] = { "r_vxyz", "r_vxyz_uncertain", "r_vang", "r_vang_uncertain", "r_xyz", "schmitt_low_threshold",
+                                                      "schmitt_high_threshold", "schmitt_low_delay", "schmitt_high_delay", "total_force",
+                                                      "standing_schmitt_level" };
+    for (size_t b = 0; b < B; b++) {
+      auto at = [&](int row) { return block[(size_t) row * B + b]; };
+      int bad = -1;
+      for (int row = 0; row < PB_LEGPAR_ROWS && bad < 0; row++) {
+        const double v = at(row);
+        const bool noise = row <= PB_LEGPAR_R_XYZ, delay = row == PB_LEGPAR_SCHMITT_LOW_DELAY || row == PB_LEGPAR_SCHMITT_HIGH_DELAY;
+        if (noise && !(std::isfinite(v) && v >= 0)) bad = row;
+        if (delay && !(v >= 0 && v <= 2e9 && v == std::floor(v))) bad = row;
+        if (row == PB_LEGPAR_SCHMITT_HIGH && !(v >= at(PB_LEGPAR_SCHMITT_LOW))) bad = row;
+      }
+      if (bad >= 0)
+        return fail(c, PB_ERR_ARG, "pb_legodo_set_param_block: filter %zu, row %d (%s) = %g: noises finite and >= 0, high >= low threshold, "
+                    "delays whole numbers in [0, 2e9] us", b, bad, name[bad], at(bad));
+    }
+  }
+  // rows `stride` apart like legd: the lanes past the batch of a tile read in bounds (zeros)
+  const bool fresh = c->leg_blk == nullptr;
+  if (int rc = dev_alloc(c, c->leg_blk, (size_t) PB_LEGPAR_ROWS * c->stride)) return rc;
+  if (fresh) HIPCHK(c, hipMemsetAsync(c->leg_blk, 0, sizeof(double) * PB_LEGPAR_ROWS * (size_t) c->stride, c->stream));
+  HIPCHK(c, hipMemcpy2DAsync(c->leg_blk, sizeof(double) * (size_t) c->stride, block, sizeof(double) * B, sizeof(double) * B, PB_LEGPAR_ROWS,
+                             mem == PB_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));  // the caller's array is free again
+  c->leg_blk_on = true;
   return PB_OK;
 }
 
@@ -354,8 +402,12 @@ static int legodo_kernel(pb_ctx *c, bool split, const LegIn &in, const LegAhead 
                          double *delta_out, double *status_out, double *lo_out, uint8_t *mask_out, double *pos_out, uint8_t *pos_ok_out)
 {
 #define LEGODO_ARGS c->st, c->legd, c->legi, c->stride, c->B, utime, c->leg_par, in, c->leg_chain, ah, zero_delta, mp, delta_out, status_out, lo_out, mask_out, pos_out, pos_ok_out, c->k
+  const LegParRows rows{ c->leg_blk, c->stride };
   with_ns(c->ns, [&](auto NS) {
-    if (split) k_legodo<decltype(NS)::value, true><<<nblk(c->B), 128, 0, c->stream>>>(LEGODO_ARGS);
+    if (c->leg_blk_on) {  // per-filter noises and contact thresholds (pb_legodo_set_param_block): the sibling kernel
+      if (split) k_odo_legpar<decltype(NS)::value, true><<<nblk(c->B), 128, 0, c->stream>>>(LEGODO_ARGS, rows);
+      else k_odo_legpar<decltype(NS)::value><<<nblk(c->B), 64, 0, c->stream>>>(LEGODO_ARGS, rows);
+    } else if (split) k_legodo<decltype(NS)::value, true><<<nblk(c->B), 128, 0, c->stream>>>(LEGODO_ARGS);
     else k_legodo<decltype(NS)::value><<<nblk(c->B), 64, 0, c->stream>>>(LEGODO_ARGS);
   });
 #undef LEGODO_ARGS

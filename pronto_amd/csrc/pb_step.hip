@@ -106,7 +106,10 @@ int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const dou
   int rc = PB_OK;
   imu = pbk_idle_prepare(c, imu, &rc);
   if (rc) return rc;
-  if (c->ns == 15) pbk_step_leg15(c, out, imu, q, bc, lin, la);
+  if (c->leg_blk_on) {  // per-filter noises and contact thresholds (pb_legodo_set_param_block): the sibling kernels
+    if (c->ns == 15) pbk_legpar15(c, out, imu, q, bc, lin, la);
+    else pbk_legpar21(c, out, imu, q, bc, lin, la);
+  } else if (c->ns == 15) pbk_step_leg15(c, out, imu, q, bc, lin, la);
   else pbk_step_leg21(c, out, imu, q, bc, lin, la);
   LAUNCHCHK(c);
   update_done(c, out);

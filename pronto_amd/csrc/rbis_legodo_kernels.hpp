@@ -1,9 +1,10 @@
 // rbis_legodo_kernels.hpp -- the stand-alone leg-odometry kernels on top of rbis_legodo.hpp: k_legodo (the odometry of one message, with
-// its measurement), k_leg_fk, k_legodo_reset and k_legodo_get.  Launched from pronto_batch.hip only, and included by it only: the last
+// its measurement) and k_odo_legpar (the same with per-filter noises and contact thresholds), k_leg_fk, k_legodo_reset and k_legodo_get.  Launched from pronto_batch.hip only, and included by it only: the last
 // three are plain (non-template) kernels, emitted by every object that sees them.
 #pragma once
 
 #include "rbis_legodo.hpp"
+#include "rbis_legpar.hpp"
 
 namespace pb {
 
@@ -21,13 +22,16 @@ struct LegAhead {
 };
 // SPLIT (per-filter joint blocks, 128-thread workgroups): a second wave runs the RIGHT leg's forward kinematics for the same 64
 // robots and hands the foot pose over through LDS -- half of the kinematics leaves the one wave's dependent chain.
-template <int NS, bool SPLIT = false>
-static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const double *__restrict__ st, double *__restrict__ legd,
-                                                         int64_t *__restrict__ legi, long stride, int B, int64_t utime, LegPar par,
-                                                         LegIn in, const LegChain *__restrict__ chain, LegAhead ah, int zero_delta, LegMeasPar mp,
-                                                         double *__restrict__ delta_out, double *__restrict__ status_out,
-                                                         double *__restrict__ lo_out, uint8_t *__restrict__ mask_out,
-                                                         double *__restrict__ pos_out, uint8_t *__restrict__ pos_ok_out, Consts k)
+// The body, shared by the kernel's two forms: SRC says where the noises and contact thresholds come from (rbis_legpar.hpp) -- the
+// kernel arguments (k_legodo) or a per-filter block (k_odo_legpar).
+template <int NS, bool SPLIT, class SRC>
+static __device__ __forceinline__ void legodo_one(const double *__restrict__ st, double *__restrict__ legd, int64_t *__restrict__ legi,
+                                                  long stride, int B, int64_t utime, const LegPar &par, const LegIn &in,
+                                                  const LegChain *__restrict__ chain, const LegAhead &ah, int zero_delta, const LegMeasPar &mp,
+                                                  double *__restrict__ delta_out, double *__restrict__ status_out,
+                                                  double *__restrict__ lo_out, uint8_t *__restrict__ mask_out,
+                                                  double *__restrict__ pos_out, uint8_t *__restrict__ pos_ok_out, const Consts &k,
+                                                  const SRC &src)
 {
   using L = Lay<NS>;
   using S = Slots<NS>;
@@ -97,7 +101,8 @@ static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const dou
   int64_t prev = 0;
   double position[3];
   bool position_ok;
-  double status = leg_update(s, par, utime, bl, br, fl, fr, ncl, ncr, wq, delta, prev, wpos, position, position_ok);
+  const unsigned bo = (unsigned) b * 8u;   // the lane's byte offset in a row of the parameter block
+  double status = leg_update(s, src.contact_par(par, bo), utime, bl, br, fl, fr, ncl, ncr, wq, delta, prev, wpos, position, position_ok);
   const bool zero = leg_zero_velocity(s, status) || zero_delta != 0;
   if (msg_ok) leg_store(s, legd, legi, stride, b, par.world_constraint != 0);
   else status = -1.0;
@@ -116,7 +121,8 @@ static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const dou
   if (status_out != nullptr) status_out[b] = status;
   if (lo_out != nullptr && mp.mode == 0) {
     LegMeas m;
-    leg_measurement(delta, status, utime, prev, mp.r_v2, mp.r_v2_uncertain, m);
+    const LegMeasPar &mq = src.meas_par(mp, bo);
+    leg_measurement(delta, status, utime, prev, mq.r_v2, mq.r_v2_uncertain, m);
     for (int i = 0; i < 3; i++) {
       lo_out[(long) i * B + b] = m.z[i];
       lo_out[(long) (3 + i) * B + b] = m.r;
@@ -124,7 +130,7 @@ static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const dou
     if (mask_out != nullptr) mask_out[b] = m.valid ? 1 : 0;
   } else if (lo_out != nullptr) {  // the six-row modes: z [6][B] | R diagonal [6][B]; masks [B] (six rows) | [B] (mode 2's lin_rate fall-back)
     LegMeas6 m;
-    leg_measurement6(delta, status, position, position_ok, utime, prev, mp, m);
+    leg_measurement6(delta, status, position, position_ok, utime, prev, src.meas_par(mp, bo), m);
     for (int i = 0; i < 6; i++) {
       lo_out[(long) i * B + b] = m.z[i];
       lo_out[(long) (6 + i) * B + b] = m.r[i];
@@ -134,6 +140,30 @@ static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const dou
       if (mp.mode == 2) mask_out[(long) B + b] = m.valid3 ? 1 : 0;
     }
   }
+}
+template <int NS, bool SPLIT = false>
+static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_legodo(const double *__restrict__ st, double *__restrict__ legd,
+                                                         int64_t *__restrict__ legi, long stride, int B, int64_t utime, LegPar par,
+                                                         LegIn in, const LegChain *__restrict__ chain, LegAhead ah, int zero_delta, LegMeasPar mp,
+                                                         double *__restrict__ delta_out, double *__restrict__ status_out,
+                                                         double *__restrict__ lo_out, uint8_t *__restrict__ mask_out,
+                                                         double *__restrict__ pos_out, uint8_t *__restrict__ pos_ok_out, Consts k)
+{
+  legodo_one<NS, SPLIT>(st, legd, legi, stride, B, utime, par, in, chain, ah, zero_delta, mp, delta_out, status_out, lo_out, mask_out, pos_out,
+                        pos_ok_out, k, LegParArgs());
+}
+// ... with the noises and contact thresholds per filter (pb_legodo_set_param_block)
+template <int NS, bool SPLIT = false>
+static __global__ __launch_bounds__(SPLIT ? 128 : 64, 2) void k_odo_legpar(const double *__restrict__ st, double *__restrict__ legd,
+                                                         int64_t *__restrict__ legi, long stride, int B, int64_t utime, LegPar par,
+                                                         LegIn in, const LegChain *__restrict__ chain, LegAhead ah, int zero_delta, LegMeasPar mp,
+                                                         double *__restrict__ delta_out, double *__restrict__ status_out,
+                                                         double *__restrict__ lo_out, uint8_t *__restrict__ mask_out,
+                                                         double *__restrict__ pos_out, uint8_t *__restrict__ pos_ok_out, Consts k,
+                                                         LegParRows rows)
+{
+  legodo_one<NS, SPLIT>(st, legd, legi, stride, B, utime, par, in, chain, ah, zero_delta, mp, delta_out, status_out, lo_out, mask_out, pos_out,
+                        pos_ok_out, k, rows);
 }
 // forward kinematics alone: feet_out [14][B] (diagnostics, tests)
 static __global__ __launch_bounds__(64) void k_leg_fk(LegIn in, const LegChain *__restrict__ chain, int B, double *__restrict__ feet_out)

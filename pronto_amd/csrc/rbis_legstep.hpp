@@ -18,6 +18,7 @@
 
 #include "rbis_tile_io.hpp"
 #include "rbis_legodo.hpp"
+#include "rbis_legpar.hpp"
 #include "rbis_quad.hpp"
 
 namespace pb {
@@ -85,10 +86,13 @@ __device__ __forceinline__ void leg_blocks(const Pose &delta, double status, con
 // SIX: LegOdoCommon's six-row modes in the same kernel (rbis_coop.hpp, coop_role_core): 1 lin_rot_rate, 2 pos_and_lin_rate (with
 // leg_estimate's world constraint: the pelvis position is measured, so the odometry wave needs the head POSITION after the IMU
 // step too -- the whole state propagate instead of the quaternion's).
-template <int NS, int MH, int PLAN = 0, int EARLY = 12, int SIX = 0>
-__global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
-                                                     double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
-                                                     const LegChain *__restrict__ chain, LegStepArgs la)
+// The body of the kernel, shared by its two forms: SRC says where the odometry's tunables come from (rbis_legpar.hpp) -- the kernel
+// arguments (k_step_leg) or a per-filter block (k_pair_legpar).  The block's rows are requested right in front of their use: the
+// Schmitt rows in front of leg_contacts, the noises in front of leg_blocks.
+template <int NS, int MH, int PLAN, int EARLY, int SIX, class SRC>
+__device__ __forceinline__ void step_leg_pair(const double *st, double *sto, int B, const double *__restrict__ imu, double qg, double qa,
+                                              double qbg, double qba, const Consts &k, const StepBcast &bc, const LegPar &par,
+                                              const LegIn &lin, const LegChain *__restrict__ chain, const LegStepArgs &la, const SRC &src)
 {
   static_assert(NS == 15, "21 states: k_step_quad_leg");
   using L = Lay<NS>;
@@ -171,7 +175,7 @@ __global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *s
     if (split_fk) {
       if (PLAN != 1) leg_fk_side(lin, chain, 1, bl_, (long) B, fr_);
       leg_inputs_rest(lin, bl_, (long) B, zl, zr, ncl, ncr);
-      if (PLAN != 0) cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);  // (needs no foot pose)
+      if (PLAN != 0) cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);  // (needs no foot pose)
       __syncthreads();  // barrier F
 #pragma unroll
       for (int i = 0; i < 3; i++) fl_.t[i] = xch[CX::XCH_FOOT + i][lane];
@@ -183,11 +187,11 @@ __global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *s
 #pragma unroll
         for (int i = 0; i < 4; i++) fr_.q[i] = xch[CX::XCH_FOOT + 10 + i][lane];
       } else if (PLAN == 0) {
-        cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);
+        cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);
       }
     } else {
       leg_inputs(lin, chain, bl_, (long) B, fl_, fr_, zl, zr, ncl, ncr);
-      cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);
+      cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);
     }
     // world_to_body_ = the head AFTER this pair's IMU step
     double wpos[3] = { 0.0, 0.0, 0.0 };
@@ -211,7 +215,7 @@ __global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *s
     if (b < (unsigned) B && msg_ok) leg_store(s, la.legd, la.legi, la.stride, (long) b, WC);
     if (!msg_ok) status = -1.0;
     LegBlocks<SIX> m;
-    leg_blocks<SIX>(delta, status, position, position_ok, ut, prev, la, b, B, m);
+    leg_blocks<SIX>(delta, status, position, position_ok, ut, prev, src.template noises<SIX>(la, bo), b, B, m);
 #pragma unroll
     for (int i = 0; i < 3; i++) xch[CX::XCH_LEG + i][lane] = m.zv[i];
     xch[CX::XCH_LEG + 3][lane] = m.rv;
@@ -237,6 +241,23 @@ __global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *s
   }
 }
 
+template <int NS, int MH, int PLAN = 0, int EARLY = 12, int SIX = 0>
+__global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
+                                                     double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
+                                                     const LegChain *__restrict__ chain, LegStepArgs la)
+{
+  step_leg_pair<NS, MH, PLAN, EARLY, SIX>(st, sto, B, imu, qg, qa, qbg, qba, k, bc, par, lin, chain, la, LegParArgs());
+}
+// ... with the odometry's noises and contact thresholds per filter (pb_legodo_set_param_block): the rows of `rows` replace par.alt,
+// par.total_force / standing_schmitt_level, la.r2 / r2_uncertain and la.mp's variances
+template <int NS, int MH, int SIX = 0>
+__global__ __launch_bounds__(128, 2) void k_pair_legpar(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
+                                                        double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
+                                                        const LegChain *__restrict__ chain, LegStepArgs la, LegParRows rows)
+{
+  step_leg_pair<NS, MH, 0, 12, SIX>(st, sto, B, imu, qg, qa, qbg, qba, k, bc, par, lin, chain, la, rows);
+}
+
 // The same for 21 states on the four-wave mapping (rbis_quad.hpp).  Role PW owns the state vector and the quaternion and
 // propagates them before barrier A anyway; it runs the odometry first, on the prior state it reads for its process blocks,
 // and publishes (z, R, valid) before that barrier -- role CC reads them behind it: no extra barrier.
@@ -249,10 +270,10 @@ __global__ __launch_bounds__(128, 2) void k_step_leg(const double *st, double *s
 //      + efforts, 64k filters, one box, min of 2 interleaved runs), PLAN 0 53.1 / 54.4 us.  (The figures below are older: before the pin.)
 // Measured (same runs): PLAN 2 51.2-51.4 us in ONE kernel, PLAN 0 54.6 us, round 3's two launches 54.2-55.7 us; panel rows of role PW
 // requested ahead of the odometry (EARLY 8 / 16) change nothing (53.1 / 51.8 us).
-template <int MH, int PLAN = 3, int EARLY = 0, int SIX = 0>
-__global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
-                                                          double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
-                                                          const LegChain *__restrict__ chain, LegStepArgs la)
+template <int MH, int PLAN, int EARLY, int SIX, class SRC>
+__device__ __forceinline__ void step_quad_leg_pair(const double *st, double *sto, int B, const double *__restrict__ imu, double qg, double qa,
+                                                   double qbg, double qba, const Consts &k, const StepBcast &bc, const LegPar &par,
+                                                   const LegIn &lin, const LegChain *__restrict__ chain, const LegStepArgs &la, const SRC &src)
 {
   constexpr int NS = 21;
   using L = Lay<NS>;
@@ -348,16 +369,16 @@ __global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, doub
     const bool msg_ok = lin.valid == nullptr || lin.valid[bl_] != 0;           // ... or no message for it at all
     if (split_fk) {
       leg_inputs_rest(lin, bl_, (long) B, zl, zr, ncl, ncr);
-      if (PLAN != 0) cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);  // (needs no foot pose)
+      if (PLAN != 0) cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);  // (needs no foot pose)
       __syncthreads();  // barrier F
 #pragma unroll
       for (int i = 0; i < 3; i++) { fl_.t[i] = xch[Quad::X_FOOT + i][lane]; fr_.t[i] = xch[Quad::X_FOOT + 7 + i][lane]; }
 #pragma unroll
       for (int i = 0; i < 4; i++) { fl_.q[i] = xch[Quad::X_FOOT + 3 + i][lane]; fr_.q[i] = xch[Quad::X_FOOT + 10 + i][lane]; }
-      if (PLAN == 0) cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);
+      if (PLAN == 0) cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);
     } else {
       leg_inputs(lin, chain, bl_, (long) B, fl_, fr_, zl, zr, ncl, ncr);
-      cs = leg_contacts(s, par, ut, zl, zr, ncl, ncr, classification, prev);
+      cs = leg_contacts(s, src.contact_par(par, bo), ut, zl, zr, ncl, ncr, classification, prev);
     }
     double wpos[3] = { 0.0, 0.0, 0.0 };
     if constexpr (WC) {
@@ -380,7 +401,7 @@ __global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, doub
     if (b < (unsigned) B && msg_ok) leg_store(s, la.legd, la.legi, la.stride, (long) b, WC);
     if (!msg_ok) status = -1.0;
     LegBlocks<SIX> m;
-    leg_blocks<SIX>(delta, status, position, position_ok, ut, prev, la, b, B, m);
+    leg_blocks<SIX>(delta, status, position, position_ok, ut, prev, src.template noises<SIX>(la, bo), b, B, m);
 #pragma unroll
     for (int i = 0; i < 3; i++) xch[Quad::X_LEG + i][lane] = m.zv[i];
     xch[Quad::X_LEG + 3][lane] = m.rv;
@@ -409,6 +430,20 @@ __global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, doub
     }
     quad_role_passive<true, 1, SIX>(ld, stf, xwr, xrd, sync, in, k);
   }
+}
+template <int MH, int PLAN = 3, int EARLY = 0, int SIX = 0>
+__global__ __launch_bounds__(256, 2) void k_step_quad_leg(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
+                                                          double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
+                                                          const LegChain *__restrict__ chain, LegStepArgs la)
+{
+  step_quad_leg_pair<MH, PLAN, EARLY, SIX>(st, sto, B, imu, qg, qa, qbg, qba, k, bc, par, lin, chain, la, LegParArgs());
+}
+template <int MH, int SIX = 0>
+__global__ __launch_bounds__(256, 2) void k_pair_quad_legpar(const double *st, double *sto, int B, const double *__restrict__ imu, double qg,
+                                                             double qa, double qbg, double qba, Consts k, StepBcast bc, LegPar par, LegIn lin,
+                                                             const LegChain *__restrict__ chain, LegStepArgs la, LegParRows rows)
+{
+  step_quad_leg_pair<MH, 3, 0, SIX>(st, sto, B, imu, qg, qa, qbg, qba, k, bc, par, lin, chain, la, rows);
 }
 #endif
 
