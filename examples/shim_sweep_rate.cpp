@@ -55,7 +55,7 @@ int main(int argc, char **argv)
   if (const char *ov = getenv("SHIM_SWEEP_OVERRIDES")) param.applyOverrides(ov);   // "key=value|key=value": extra BotParam keys (experiments)
   param.set("state_estimator.utime_history_span", span);
   // "derived": only utime_history_span is set, like every reference .cfg -- the estimator then derives its checkpoint pool
-  // (32 slots spaced over the span, mav_state_est_batch.hpp)
+  // (32 slots spaced over the span, mav_state_est.hpp)
   if (slots != "derived") param.set("state_estimator.history_slots", slots);
   param.set("state_estimator.fuse_ins_legodo", "true");
   param.set("state_estimator.ins.channel", "IMU");

@@ -20,7 +20,7 @@ def build_exe(oracle, name="test_shim"):
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
     deps = [src, os.path.join(ROOT, "tests", "cpp", "test_n.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est_batch.hpp"),
-            os.path.join(ROOT, "pronto_amd", "csrc", "segment_batcher.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "segment_stream.hpp"),
+            os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "segment_batcher.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "segment_stream.hpp"),
             os.path.join(ROOT, "pronto_amd", "csrc", "lcm_schema.hpp"),
             os.path.join(ROOT, "pronto_amd", "csrc", "pronto_wire.hpp"),
             os.path.join(ROOT, "include", "pronto_batch.h"), _lib.LIB_PATH]
@@ -259,7 +259,8 @@ def build_shim_sweep_rate():
     exe = os.path.join(ROOT, "tests", "build", "shim_sweep_rate")
     os.makedirs(os.path.dirname(exe), exist_ok=True)
     src = os.path.join(ROOT, "examples", "shim_sweep_rate.cpp")
-    deps = (src, _lib.LIB_PATH, os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est_batch.hpp"))
+    deps = (src, _lib.LIB_PATH, os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est_batch.hpp"),
+            os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est.hpp"))
     if os.path.exists(exe) and all(os.path.getmtime(exe) >= os.path.getmtime(d) for d in deps):
         return exe
     subprocess.check_call(["g++", "-std=c++17", "-O2", "-Wall", "-I" + os.path.join(ROOT, "include"),
