@@ -479,7 +479,12 @@ int pb_ins_body_reset(pb_ctx *ctx);
  * replaces, right in front of the step kernel, the sample of such a filter by the one that reproduces its angular-velocity and
  * acceleration entries too (omega + gyro bias, a + accel bias of the prior), and sets its dt to 0: the step is a no-op for it --
  * exactly for 15 states, to the last bit of those sums for 21 -- and a measurement update in the same kernel sees the state the
- * reference's would.  The step kernels themselves know nothing of it.  The array must stay valid until the step has run. */
+ * reference's would.  One thing a process step does whatever dt: it overwrites the angular-velocity and the acceleration diagonal
+ * block of the covariance with q_gyro I and q_accel I (rbis.cpp:120-121); behind the step kernel the library puts the prior's blocks
+ * back for these filters (bit for bit; where a correction in the same call has downdated them, with that downdate kept).
+ * The step kernels themselves know nothing of it.  The array must stay valid until the step has run.
+ * The mask applies wherever that call's IMU sample lives: a PB_HOST_BROADCAST sample (one for every filter, otherwise passed as
+ * kernel arguments) is covered too -- under a mask it is expanded on the device into the prepared block the step reads. */
 int pb_set_imu_valid(pb_ctx *ctx, const uint8_t *valid_dev);
 
 /* ---- posterior checkpoints for roll-forward replay (mav_state_est.cpp:28-80, update_history.cpp) ------------ */

@@ -310,6 +310,13 @@ class BatchEstimator:
         p, m = _ptr_block(n_contacts, 2, self.B, dtype=np.int32)
         self._chk(self._L.pb_legodo_set_control_contacts(self._h, p, m))
 
+    def legodo_set_message_times(self, utimes=None, valid=None):
+        """Per-filter message times [B] int64 and / or validity [B] uint8 of the NEXT odometry or pair call (pb_legodo_set_message_times):
+        numpy arrays (copied) or device tensors (read in place by that call: keep them alive until it has run)."""
+        pu, m1 = _ptr(utimes, np.int64, shape=(self.B,))
+        pv, m2 = _ptr(valid, np.uint8, shape=(self.B,))
+        self._chk(self._L.pb_legodo_set_message_times(self._h, pu, pv, PB_HOST if utimes is None and valid is None else _same_mem(m1, m2)))
+
     def legodo_set_chain(self, n_left, n_right, joint_type, joint_row, origin_xyz_rpy, axis, adjustment_gain=None):
         n = n_left + n_right
         ty = (C.c_int * n)(*[int(v) for v in joint_type])
@@ -554,6 +561,47 @@ class BatchEstimator:
         pi, m1 = _ptr(accel_packets, shape=(accel_packets.shape[0], 3, self.B))
         po_, m2 = _ptr(accel_out, shape=(3, self.B))
         self._chk(self._L.pb_imu_notch(self._h, accel_packets.shape[0], pi, po_, _same_mem(m1, m2)))
+
+    def imu_notch_counts(self, counts, accel_packets, accel_out):
+        """imu_notch with a packet count per filter (pb_imu_notch_counts): counts [B] int32, accel_packets [max_packets,3,B]; a filter
+        without a new packet keeps its accel_out entries (device tensors) or gets 0 (numpy)."""
+        if accel_packets.ndim != 3:
+            raise ValueError("accel_packets must be [max_packets, 3, B]")
+        pc, m0 = _ptr(counts, np.int32, shape=(self.B,))
+        pi, m1 = _ptr(accel_packets, shape=(accel_packets.shape[0], 3, self.B))
+        po_, m2 = _ptr(accel_out, shape=(3, self.B))
+        self._chk(self._L.pb_imu_notch_counts(self._h, accel_packets.shape[0], pc, pi, po_, _same_mem(m0, m1, m2)))
+
+    def ins_body_block(self, gyro, accel, rot_quat, imu_block_out, raw_dt=None, utimes=None, utime=0, valid=None, trans_vec=None,
+                       dt_default=0.0, dt_from_utimes=False, valid_out=None):
+        """InsHandler's per-message arithmetic (pb_ins_body_block): gyro / accel [3,B], raw_dt [B], utimes [B] int64, valid [B] uint8 live
+        in one space (numpy or device tensors); rot_quat (w, x, y, z) and trans_vec are 4 / 3 values; imu_block_out [7,B] and valid_out
+        [B] uint8 are device tensors."""
+        pg, m1 = _ptr(gyro, shape=(3, self.B))
+        pa, m2 = _ptr(accel, shape=(3, self.B))
+        pr, m3 = _ptr(raw_dt, shape=(self.B,))
+        pu, m4 = _ptr(utimes, np.int64, shape=(self.B,))
+        pv, m5 = _ptr(valid, np.uint8, shape=(self.B,))
+        po_, mo = _ptr(imu_block_out, shape=(7, self.B))
+        pvo, mvo = _ptr(valid_out, np.uint8, shape=(self.B,))
+        if mo != PB_DEVICE or (valid_out is not None and mvo != PB_DEVICE):
+            raise ValueError("ins_body_block outputs must be device tensors")
+        rq = (C.c_double * 4)(*rot_quat)
+        tv = None if trans_vec is None else (C.c_double * 3)(*trans_vec)
+        self._chk(self._L.pb_ins_body_block(self._h, pg, pa, pr, pu, int(utime), pv, rq, tv, float(dt_default), int(bool(dt_from_utimes)),
+                                            _same_mem(m1, m2, m3, m4, m5), po_, pvo))
+
+    def ins_body_reset(self):
+        """forget every filter's last body-frame sample and previous message time (pb_ins_body_reset)"""
+        self._chk(self._L.pb_ins_body_reset(self._h))
+
+    def set_imu_valid(self, valid_dev):
+        """valid_dev [B] uint8 device tensor (0 = no IMU message), or None: for the NEXT call that takes an IMU step (pb_set_imu_valid);
+        the tensor must stay alive until that step has run."""
+        p, m = _ptr(valid_dev, np.uint8, shape=(self.B,))
+        if valid_dev is not None and m != PB_DEVICE:
+            raise ValueError("the IMU validity mask must be a device tensor")
+        self._chk(self._L.pb_set_imu_valid(self._h, p))
 
     # --- update objects ---
     def reset(self, vec, quat, cov, broadcast=False):

@@ -94,7 +94,9 @@ struct pb_ctx {
   int64_t *ins_prev_ut = nullptr;
   const uint8_t *imu_valid_next = nullptr;   // pb_set_imu_valid: one-shot, taken by the next call that takes an IMU step (Call) ...
   const uint8_t *imu_valid_cur = nullptr;    // ... and held here for the duration of that call
-  double *imu_keep = nullptr;                // [7][stride]: the IMU block that call's step kernel reads instead (pbk_idle_prepare)
+  double *imu_keep = nullptr;                // [7][B]: the IMU block that call's step kernel reads instead (pbk_idle_prepare), and behind
+                                             // it [12][B]: the idle filters' omega / acceleration covariance blocks (pbk_idle_restore)
+  const uint8_t *imu_idle_cur = nullptr;     // the mask pbk_idle_prepare applied in this call: its step launches are followed by pbk_idle_restore
   // chunked uploads (pb_upload_async): fences recorded on the main stream, one event for "the uploads issued so far"
   hipEvent_t fence[PB_MAX_FENCES] = {};
   int n_fences = 0;
@@ -283,7 +285,7 @@ struct Call {
   ~Call()
   {
     if (!c) return;
-    if (what & IMU_STEP) c->imu_valid_cur = nullptr;
+    if (what & IMU_STEP) c->imu_valid_cur = c->imu_idle_cur = nullptr;
     if (what & PRED_TAKE) c->pred_slot = -1;
   }
 
@@ -325,8 +327,13 @@ struct Call {
 
 // in front of the ONE step launch of a call that was given a mask (pb_set_imu_valid): the IMU block with the samples of the filters
 // WITHOUT a message replaced by what reproduces their angular-velocity / acceleration entries (pb_frontend.hip); the block itself
-// when there is no mask
-const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out);
+// when there is no mask.  bc: the call's own copy of its broadcast inputs -- a broadcast IMU sample under a mask becomes a prepared
+// block as well, and bc's IMU bit is cleared so that the step reads it
+const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, StepBcast &bc, int *rc_out);
+// behind every step launch of such a call: the process step overwrites the omega and acceleration diagonal blocks of the covariance
+// with q_gyro I, q_accel I whatever dt (rbis.cpp:120-121), which the reference did not do for a filter without a message -- they are
+// put back (out: the posterior; pred: the predicted slot written by the same launch, or NULL).  Nothing without a mask.
+int pbk_idle_restore(pb_ctx *c, double *out, double *pred, const double q[4]);
 
 // ---- launchers defined in the other translation units ----
 // pb_step.hip: predict (update = false) or predict + leg-odometry update on the kernel pb_create picked

@@ -12,20 +12,42 @@ extern "C" int pb_set_imu_valid(pb_ctx *c, const uint8_t *valid_dev)
   return PB_OK;
 }
 // The call that takes the mask (CALL: IMU_STEP) holds it in imu_valid_cur; the launchers of the step kernels (pb_step.hip) pass their
-// IMU block through pbk_idle_prepare right in front of their ONE launch (rbis_frontend.hpp, k_imu_idle_prepare).
-const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, int *rc_out)
+// IMU block through pbk_idle_prepare right in front of their ONE launch (rbis_frontend.hpp, k_imu_idle_prepare).  A broadcast sample
+// (bc.on bit 0: no block, the seven values are kernel arguments) is expanded into the prepared block and the bit cleared in the
+// caller's copy of bc, so that the step reads that block like any other.
+const double *pbk_idle_prepare(pb_ctx *c, const double *imu_dev, StepBcast &bc, int *rc_out)
 {
   *rc_out = PB_OK;
   const uint8_t *valid = c->imu_valid_cur;
-  if (!valid || !imu_dev) return imu_dev;
+  const bool one = (bc.on & 1) != 0;
+  if (!valid || (!imu_dev && !one)) return imu_dev;
   c->imu_valid_cur = nullptr;   // (one step launch per call)
-  if ((*rc_out = dev_alloc(c, c->imu_keep, 7 * (size_t) c->stride))) return imu_dev;
+  if ((*rc_out = dev_alloc(c, c->imu_keep, (7 + 12) * (size_t) c->stride))) return imu_dev;
+  ImuSample s;
+  for (int i = 0; i < 7; i++) s.v[i] = bc.imu[i];
   with_ns(c->ns, [&](auto NS) {
-    k_imu_idle_prepare<decltype(NS)::value><<<(c->B + 255) / 256, 256, 0, c->stream>>>(c->st, valid, imu_dev, c->imu_keep, c->B);
+    k_imu_idle_prepare<decltype(NS)::value><<<(c->B + 255) / 256, 256, 0, c->stream>>>(c->st, valid, one ? nullptr : imu_dev, s, c->imu_keep,
+                                                                                       c->imu_keep + 7 * (size_t) c->B, c->B);
   });
   hipError_t e = hipGetLastError();
-  if (e != hipSuccess) *rc_out = fail(c, PB_ERR_HIP, "k_imu_idle_prepare: %s", hipGetErrorString(e));
+  if (e != hipSuccess) {
+    *rc_out = fail(c, PB_ERR_HIP, "k_imu_idle_prepare: %s", hipGetErrorString(e));
+    return imu_dev;
+  }
+  bc.on &= ~1;
+  c->imu_idle_cur = valid;
   return c->imu_keep;
+}
+
+int pbk_idle_restore(pb_ctx *c, double *out, double *pred, const double q[4])
+{
+  if (!c->imu_idle_cur) return PB_OK;
+  with_ns(c->ns, [&](auto NS) {
+    k_imu_idle_restore<decltype(NS)::value><<<(c->B + 255) / 256, 256, 0, c->stream>>>(out, pred, c->imu_idle_cur, c->imu_keep + 7 * (size_t) c->B,
+                                                                                       q[0], q[1], c->k.qblk, c->B);
+  });
+  LAUNCHCHK(c);
+  return PB_OK;
 }
 
 extern "C" int pb_imu_notch_init(pb_ctx *c, double notch_freq, double fs)

@@ -28,16 +28,18 @@ static void launch_step_kernel(pb_ctx *c, const double *st, double *out, int nb,
 }
 
 template <bool UPDATE>
-static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bc)
+static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bcast)
 {
   double *out = update_target(c);
   int rc = PB_OK;
-  imu = pbk_idle_prepare(c, imu, &rc);
+  StepBcast bc = bcast;
+  imu = pbk_idle_prepare(c, imu, bc, &rc);
   if (rc) return rc;
   with_mem_hint(c->mem_hint, [&](auto mh) {
     launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->coop15, c->half15, imu, lo, mask, q, bc);
   });
   LAUNCHCHK(c);
+  if ((rc = pbk_idle_restore(c, out, nullptr, q))) return rc;
   update_done(c, out);
   return PB_OK;
 }
@@ -62,17 +64,19 @@ int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t
 // The fused step with a predicted slot pending (pb_set_pred_slot, consumed here): one launch that writes both posteriors where a kernel
 // for it exists (k_step_coop_pred), otherwise the predict alone into the slot -- the head stays where it is -- and the fused step
 // behind it.  Either way the filtered posterior is the fused step's, bit for bit, and the slot holds what pb_predict would leave.
-static int step_pred(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bc)
+static int step_pred(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], const StepBcast &bcast)
 {
   double *pred = slot_ptr(c, c->pred_slot);
   const int ps = c->pred_slot;
   c->pred_slot = -1;
   int rc = PB_OK;
-  imu = pbk_idle_prepare(c, imu, &rc);   // (once: both launches of the fall-back read the same prepared block)
+  StepBcast bc = bcast;
+  imu = pbk_idle_prepare(c, imu, bc, &rc);   // (once: both launches of the fall-back read the same prepared block)
   if (rc) return rc;
   double *out = update_target(c);
   if (pbk_step_pred_kernel(c, out, pred, imu, lo, mask, q, bc) == PB_OK) {
     LAUNCHCHK(c);
+    if ((rc = pbk_idle_restore(c, out, pred, q))) return rc;
     update_done(c, out);
     return PB_OK;
   }
@@ -100,11 +104,11 @@ int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const dou
   // the two-wave 15-state mapping (the default up to 393 216 filters) and the four-wave 21-state mapping.  Mode lin_rate with
   // leg_estimate's world constraint switched on needs the stand-alone kernel (mode pos_and_lin_rate tracks it inside the pair kernel).
   if ((c->ns == 15 && !c->coop15) || (c->ns == 21 && !c->quad21) || (c->leg_par.world_constraint && mp.mode != 2)) return -1;
-  const StepBcast bc = bcast ? *bcast : StepBcast();
+  StepBcast bc = bcast ? *bcast : StepBcast();
   LegStepArgs la{ c->legd, c->legi, c->stride, utime, mp.r_v2, mp.r_v2_uncertain, lo_out, mask_out, mp };
   double *out = update_target(c);
   int rc = PB_OK;
-  imu = pbk_idle_prepare(c, imu, &rc);
+  imu = pbk_idle_prepare(c, imu, bc, &rc);
   if (rc) return rc;
   if (c->leg_blk_on) {  // per-filter noises and contact thresholds (pb_legodo_set_param_block): the sibling kernels
     if (c->ns == 15) pbk_legpar15(c, out, imu, q, bc, lin, la);
@@ -112,6 +116,7 @@ int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const dou
   } else if (c->ns == 15) pbk_step_leg15(c, out, imu, q, bc, lin, la);
   else pbk_step_leg21(c, out, imu, q, bc, lin, la);
   LAUNCHCHK(c);
+  if ((rc = pbk_idle_restore(c, out, nullptr, q))) return rc;
   update_done(c, out);
   return PB_OK;
 }
@@ -177,13 +182,13 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
     for (int i = 0; i < m2; i++) ca.zb2[i] = zb[i];
     for (int i = 0; i < 4; i++) ca.qb2[i] = qb[i];
   }
-  const StepBcast bc = bcast ? *bcast : StepBcast();
+  StepBcast bc = bcast ? *bcast : StepBcast();
   // a predicted slot pending (pb_set_pred_slot, consumed here): the kernel that also stores the INS posterior (pb_step_corr_pred.hip)
   double *pred = c->pred_slot >= 0 ? slot_ptr(c, c->pred_slot) : nullptr;
   c->pred_slot = -1;
   double *out = update_target(c);
   int rc = PB_OK;
-  imu = pbk_idle_prepare(c, imu, &rc);
+  imu = pbk_idle_prepare(c, imu, bc, &rc);
   if (rc) return rc;
   if (pred) {
     if (pbk_step_corr_pred_kernel(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc)) return fail(c, PB_ERR_STATE, "pb_step_legodo_correct: no kernel keeps the prediction here");
@@ -194,6 +199,7 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
     });
   }
   LAUNCHCHK(c);
+  if ((rc = pbk_idle_restore(c, out, pred, q))) return rc;
   update_done(c, out);
   return PB_OK;
 }

@@ -138,10 +138,17 @@ static __global__ void k_ins_body(int B, long stride, const double *__restrict__
 // step is about to read: the step then re-derives what is there (exactly for 15 states, to the last bit of the sum for 21) and the
 // update that shares the kernel sees the same state the reference's would.  One small launch and a 56-byte copy per filter in
 // front of the hot kernel instead of selects inside it -- measured: the selects cost k_step_quad 6-7 % (39.7 vs 37.0-37.9 us at
-// 64k filters, same box); this costs the hot kernels nothing, and nothing at all when no mask is given.
+// 64k filters, same box); this costs the hot kernels nothing, and nothing at all when no mask is given.  What a call WITH a mask
+// pays -- this launch in front of the step and k_imu_idle_restore behind it (behind each of the two launches in step_pred's
+// fall-back), 7 + 12 doubles per filter -- has not been measured: the benchmark runs without masks.
+// imu == NULL: ONE sample for every filter (PB_HOST_BROADCAST), the seven values in `one` -- the prepared block is then the only
+// block there is, and the step reads it in place of its broadcast arguments.
+struct ImuSample {
+  double v[7];
+};
 template <int NS>
 static __global__ void k_imu_idle_prepare(const double *__restrict__ st, const uint8_t *__restrict__ valid, const double *__restrict__ imu,
-                                          double *__restrict__ imu_out, int B)
+                                          ImuSample one, double *__restrict__ imu_out, double *__restrict__ cov_keep, int B)
 {
   using L = Lay<NS>;
   using S = Slots<NS>;
@@ -149,7 +156,7 @@ static __global__ void k_imu_idle_prepare(const double *__restrict__ st, const u
   if (b >= B) return;
   double v[7];
 #pragma unroll
-  for (int i = 0; i < 7; i++) v[i] = imu[(long) i * B + b];
+  for (int i = 0; i < 7; i++) v[i] = imu ? imu[(long) i * B + b] : one.v[i];
   if (valid[b] == 0) {
 #pragma unroll
     for (int i = 0; i < 3; i++) {
@@ -157,9 +164,57 @@ static __global__ void k_imu_idle_prepare(const double *__restrict__ st, const u
       v[3 + i] = st[S::eidx(L::OFF_VEC + 12 + i, b)] + (NS == 21 ? st[S::eidx(L::OFF_VEC + (NS == 21 ? 18 : 0) + i, b)] : 0.0);
     }
     v[6] = 0.0;
+    // ... and the two covariance blocks the step overwrites whatever dt, for k_imu_idle_restore
+#pragma unroll
+    for (int blk = 0; blk < 2; blk++)
+#pragma unroll
+      for (int e = 0; e < 6; e++)
+        cov_keep[(long) (6 * blk + e) * B + b] = st[S::eidx(L::OFF_P + pk(12 * blk + pk_row(e), 12 * blk + pk_col(e)), b)];
   }
 #pragma unroll
   for (int i = 0; i < 7; i++) imu_out[(long) i * B + b] = v[i];
+}
+
+// Behind the step kernel of a call with a mask: the process step sets the omega and the acceleration diagonal block of the covariance to
+// q_gyro I and q_accel I whatever dt (rbis.cpp:120-121) -- for a filter without a message the reference did not.  Where the block is
+// still exactly that (no update in the same kernel touched it) the prior block comes back bit for bit; where an update behind the
+// step has downdated it (a correction for a filter without an IMU message) the downdate is kept: block + (prior - q I).  `pred`
+// (optional) is the predicted posterior the same launch wrote: the process step alone, so the prior block.  keep [12][B] as saved by
+// k_imu_idle_prepare; qblk (optional) [4][B]: the per-filter process noise the step used.
+// The bit-for-bit half rests on two things: q here is the very double the step kernel wrote (the same kernel argument, or the same
+// qblk entry), and an update that is masked off for a filter leaves its covariance bit-identical -- the kernels run masked lanes
+// through the same stream with D^-1 = 0 (measurement_update), so every entry gets P - 0.  Were either not so, `fresh` would be false
+// and the block would come back to rounding only; tests/test_ragged_batches.py holds both, with and without qblk, bit for bit.
+template <int NS>
+static __global__ void k_imu_idle_restore(double *__restrict__ out, double *__restrict__ pred, const uint8_t *__restrict__ valid,
+                                          const double *__restrict__ keep, double qg, double qa, const double *__restrict__ qblk, int B)
+{
+  using L = Lay<NS>;
+  using S = Slots<NS>;
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B || valid[b] != 0) return;
+  if (qblk) {
+    qg = qblk[b];
+    qa = qblk[(long) B + b];
+  }
+#pragma unroll
+  for (int blk = 0; blk < 2; blk++) {
+    const double q = blk ? qa : qg;
+    double cur[6], old[6];
+    bool fresh = true;
+#pragma unroll
+    for (int e = 0; e < 6; e++) {
+      cur[e] = out[S::eidx(L::OFF_P + pk(12 * blk + pk_row(e), 12 * blk + pk_col(e)), b)];
+      old[e] = keep[(long) (6 * blk + e) * B + b];
+      fresh = fresh && cur[e] == (pk_row(e) == pk_col(e) ? q : 0.0);
+    }
+#pragma unroll
+    for (int e = 0; e < 6; e++) {
+      const long at = S::eidx(L::OFF_P + pk(12 * blk + pk_row(e), 12 * blk + pk_col(e)), b);
+      out[at] = fresh ? old[e] : cur[e] + (old[e] - (pk_row(e) == pk_col(e) ? q : 0.0));
+      if (pred) pred[at] = old[e];
+    }
+  }
 }
 
 }  // namespace pb

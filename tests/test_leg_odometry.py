@@ -70,17 +70,24 @@ class OracleLegs:
                 self.L.po_leg_set_contact_mode(b, int(standing is not None), tf, lvl, int(use_controller_input))
         self.B = B
 
-    def update(self, utime, feet, forces, wq, nc=(-1, -1), wpos=None):
-        """-> increment [7,B], status [B], previous utime [B]; self.pos [3,B] / self.pos_ok [B] = the world constraint."""
+    def update(self, utime, feet, forces, wq, nc=(-1, -1), wpos=None, valid=None):
+        """-> increment [7,B], status [B], previous utime [B]; self.pos [3,B] / self.pos_ok [B] = the world constraint.
+        utime: one message time, or [B] (every filter's own); valid [B] (optional): a filter with 0 has no message -- its
+        po_leg_update* is not called at all and it reports status -1."""
         B = self.B
         self.pos, self.pos_ok = np.zeros((3, B)), np.zeros(B, dtype=bool)
         delta, status, prev = np.zeros((7, B)), np.zeros(B), np.zeros(B, dtype=np.int64)
         dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))
+        utimes = np.broadcast_to(np.asarray(utime, dtype=np.int64), (B,))
         for b in range(B):
+            if valid is not None and not valid[b]:
+                status[b] = -1.0
+                continue
+            ut_b = int(utimes[b])
             f = np.ascontiguousarray(feet[:, b]); w = np.ascontiguousarray(wq[:, b])
             dt, dq, pv, cp, cok = np.zeros(3), np.zeros(4), C.c_long(0), np.zeros(3), C.c_int(0)
             wp = np.zeros(3) if wpos is None else np.ascontiguousarray(wpos[:, b])
-            status[b] = self.L.po_leg_update_wc(self.bufs[b], utime, dp(f[0:3]), dp(f[3:7]), dp(f[7:10]), dp(f[10:14]), forces[0, b],
+            status[b] = self.L.po_leg_update_wc(self.bufs[b], ut_b, dp(f[0:3]), dp(f[3:7]), dp(f[7:10]), dp(f[10:14]), forces[0, b],
                                                 forces[1, b], int(nc[0]), int(nc[1]), dp(wp), dp(w), dp(dt), dp(dq), C.byref(pv), dp(cp),
                                                 C.byref(cok))
             delta[0:3, b], delta[3:7, b], prev[b] = dt, dq, pv.value
