@@ -235,9 +235,19 @@ int pb_compose_delta(pb_ctx *ctx, int slot, const double *t, const double *q, do
 /* ---- noise identification / parameter sweeps (state-estimator/src/noise_id/noise_id.cpp:9-65) ------------------ */
 
 /* Per-filter process noise: q_block [4][B] (device memory) = q_gyro, q_accel, q_gyro_bias, q_accel_bias of every
- * filter, used by all following pb_predict / pb_step_legodo / pb_run_legodo calls instead of their scalar q; NULL
- * switches back.  This is what lets ONE batch carry the windows x candidate-noise grid of a noise-ID run
- * (sampleProcessForward, noise_id.cpp:9-42: by linearity rolled_cov - start_window_cov is the predict chain from P = 0). */
+ * filter, used instead of the scalar q of the call by EVERY following call that takes a process step; NULL switches back.  The
+ * block is read in place at each launch (keep it alive and unchanged while calls are in flight).  The calls that honour it:
+ *   pb_predict, pb_step_legodo, pb_step_legodo_split, pb_step_legodo_correct -- with or without pb_set_output_slot /
+ *     pb_set_pred_slot (the predicted slot holds the per-filter process step) and under pb_set_imu_valid (what is put back for an
+ *     idle filter is measured against ITS q);
+ *   pb_run_legodo in both launch orders (the cache-blocked order hands every block of filters its own columns of q_block);
+ *   pb_replay_legodo_fused, pb_replay_legodo_checkpointed;
+ *   pb_step_legodo_feet, pb_step_legodo_joints, alone or together with pb_legodo_set_param_block;
+ *   pb_smooth_log, pb_smooth_log_fused, pb_smooth_log_corrected (the forward and the recompute pass).
+ * 15 states have no bias states: rows 2 and 3 are never read into the arithmetic there.  tests/test_process_noise_block.py holds
+ * each of these against the oracle run with every filter's own q.  This is what lets ONE batch carry the windows x candidate-noise
+ * grid of a noise-ID run (sampleProcessForward, noise_id.cpp:9-42: by linearity rolled_cov - start_window_cov is the predict chain
+ * from P = 0) or a process-noise sweep over one log (examples/param_sweep.c). */
 int pb_set_process_noise_block(pb_ctx *ctx, const double *q_block_dev);
 /* Window likelihood pieces (noise_id.cpp:37-38,44-65): e = head (-) truth with chi = Log(truth.quat^-1 * quat); over
  * the m <= 9 active indices: out3 [3][B] = log det P_aa, e_a^T P_aa^-1 e_a, -0.5*(m log 2pi + logdet + maha).

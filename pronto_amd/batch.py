@@ -256,17 +256,24 @@ class BatchEstimator:
         self._chk(self._L.pb_set_process_noise_block(self._h, p))
 
     def window_nll(self, idx, truth_vec, truth_quat, want_err=False):
-        """(logdet, maha, nll) [3,B] (+ error vector [n,B]) of head (-) truth over the active indices."""
+        """(logdet, maha, nll) [3,B] (+ error vector [n,B]) of head (-) truth over the active indices.  Truth arrays in numpy: numpy
+        results (PB_HOST); torch CUDA tensors: the results are CUDA tensors written by the kernel in place (PB_DEVICE, stream-ordered on
+        the context's stream -- sync() before reading them on another)."""
         m = len(idx)
         ia = (C.c_int * m)(*[int(i) for i in idx])
-        out = np.empty((3, self.B))
-        err = np.empty((self.n, self.B)) if want_err else None
         pv, m1 = _ptr(truth_vec, shape=(self.n, self.B))
         pq, m2 = _ptr(truth_quat, shape=(4, self.B))
-        if _same_mem(m1, m2) != PB_HOST:
-            raise ValueError("window_nll takes host truth arrays")
-        self._chk(self._L.pb_window_nll(self._h, m, ia, pv, pq, C.c_void_p(out.ctypes.data),
-                                        C.c_void_p(err.ctypes.data) if want_err else None, PB_HOST))
+        mem = _same_mem(m1, m2)
+        if mem == PB_DEVICE:
+            import torch
+            out = torch.empty((3, self.B), dtype=torch.float64, device=truth_vec.device)
+            err = torch.empty((self.n, self.B), dtype=torch.float64, device=truth_vec.device) if want_err else None
+        else:
+            out = np.empty((3, self.B))
+            err = np.empty((self.n, self.B)) if want_err else None
+        po, _ = _ptr(out)
+        pe, _ = _ptr(err)
+        self._chk(self._L.pb_window_nll(self._h, m, ia, pv, pq, po, pe, mem))
         return (out, err) if want_err else out
 
     # --- leg kinematic odometry ---

@@ -114,6 +114,7 @@ struct pb_ctx {
   int64_t utime = 0;
   bool have_state = false;
   bool half15 = false;  // the 15-state fused step with two workgroups per tile (pb_create: batches that leave half the workgroup slots empty; PRONTO_BATCH_HALF=0/1)
+  bool replay_onelane = false;  // pb_replay_legodo_fused on the first, one-lane-per-filter kernel (15 states; PRONTO_BATCH_REPLAY_ONELANE=1, read by pb_create as every other switch)
   bool coop15 = false;  // PRONTO_BATCH_COOP15=1: run the 15-state step on the two-wave cooperative kernel (A/B switch)
   int mem_hint = 0;     // MH_* cache policy of the step kernels' state round trip (PRONTO_BATCH_MEMHINT=0/1/2 forces it)
   // pb_run_legodo's cache-blocked order (filter range outer, time inner) for states beyond the memory-side cache: filters per block

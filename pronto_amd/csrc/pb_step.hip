@@ -8,22 +8,22 @@
 // cooperative launch only.
 template <bool UPDATE, int MH>
 static void launch_step_kernel(pb_ctx *c, const double *st, double *out, int nb, bool coop15, bool half, const double *imu, const double *lo,
-                               const uint8_t *mask, const double q[4], const StepBcast &bc)
+                               const uint8_t *mask, const double q[4], const StepBcast &bc, const Consts &k)
 {
   const int B = c->B;
   if (c->ns == 15 && coop15) {
-    Consts kk = c->k;
+    Consts kk = k;
     kk.half_tiles = half ? 1 : 0;   // (this launch only: every other kernel that takes c->k keeps whole tiles)
     k_step_coop<15, UPDATE, MH><<<nblk(nb) * (half ? 2 : 1), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, CorrArgs(), bc);
   } else if (c->ns == 15) {
-    k_step<15, UPDATE, MH><<<(nb + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    k_step<15, UPDATE, MH><<<(nb + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, bc);
   } else if (c->quad21) {
     // n = 21: 231 packed covariance entries do not fit one lane's registers; four cooperating waves per tile at two waves
     // per SIMD (rbis_quad.hpp): one launch, one state round trip.
-    k_step_quad<UPDATE, MH><<<nblk(nb), 256, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, bc);
+    k_step_quad<UPDATE, MH><<<nblk(nb), 256, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, bc);
   } else {
     // the two-wave cooperative kernel at one wave per SIMD (rbis_coop.hpp); PRONTO_BATCH_QUAD21=0
-    k_step_coop<21, UPDATE, MH><<<nblk(nb), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, CorrArgs(), bc);
+    k_step_coop<21, UPDATE, MH><<<nblk(nb), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, CorrArgs(), bc);
   }
 }
 
@@ -36,7 +36,7 @@ static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uin
   imu = pbk_idle_prepare(c, imu, bc, &rc);
   if (rc) return rc;
   with_mem_hint(c->mem_hint, [&](auto mh) {
-    launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->coop15, c->half15, imu, lo, mask, q, bc);
+    launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->coop15, c->half15, imu, lo, mask, q, bc, c->k);
   });
   LAUNCHCHK(c);
   if ((rc = pbk_idle_restore(c, out, nullptr, q))) return rc;
@@ -45,7 +45,8 @@ static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uin
 }
 
 // The fused step on the filters [b0, b0 + nb) only -- b0 and the batch multiples of 64 (whole tiles), the posterior in place, the inputs
-// still blocks [rows][B] of the WHOLE batch (the block is addressed by shifting every pointer).
+// still blocks [rows][B] of the WHOLE batch (the block is addressed by shifting every pointer, the per-filter process noise included:
+// the kernels count filters from 0, so an unshifted block would give every range the noise of filters 0..nb-1).
 // coop15 / mem_hint are the caller's: a block that fits the memory-side cache wants the kernel and the cache policy of ITS size.
 int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, bool coop15, int mem_hint)
 {
@@ -54,8 +55,10 @@ int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t
   const size_t tile_doubles = c->state_doubles / (size_t) (c->stride / 64);
   double *st = c->st + (size_t) (b0 / 64) * tile_doubles;
   const uint8_t *mask_b = mask ? mask + b0 : nullptr;
+  Consts kk = c->k;   // (this launch only)
+  if (kk.qblk) kk.qblk += b0;
   with_mem_hint(mem_hint, [&](auto mh) {
-    launch_step_kernel<true, decltype(mh)::value>(c, st, st, nb, coop15, false, imu + b0, lo + b0, mask_b, q, StepBcast());
+    launch_step_kernel<true, decltype(mh)::value>(c, st, st, nb, coop15, false, imu + b0, lo + b0, mask_b, q, StepBcast(), kk);
   });
   LAUNCHCHK(c);
   return PB_OK;
@@ -128,9 +131,8 @@ int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, cons
     so.base = slot_ptr(c, slot0);
     so.stride = c->state_doubles;
   }
-  // PRONTO_BATCH_REPLAY_ONELANE=1: the first, one-lane-per-filter version (15 states only; A/B runs)
-  static const bool one_lane = getenv("PRONTO_BATCH_REPLAY_ONELANE") && getenv("PRONTO_BATCH_REPLAY_ONELANE")[0] == '1';
-  if (c->ns == 15 && one_lane && slot0 < 0)
+  // PRONTO_BATCH_REPLAY_ONELANE=1 (pb_create): the first, one-lane-per-filter version (15 states only; A/B runs)
+  if (c->ns == 15 && c->replay_onelane && slot0 < 0)
     k_replay_fused<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k);
   else if (c->ns == 15)
     k_replay_coop<15><<<nblk(c->B), 128, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so);

@@ -52,6 +52,9 @@ extern "C" int pb_create(pb_ctx **out, int n_states, int batch, int device, int 
     // switch (PRONTO_BATCH_HALF=1), off by default.
     const char *eh = getenv("PRONTO_BATCH_HALF");
     c->half15 = c->coop15 && n_states == 15 && eh && eh[0] == '1';
+    // (read here, per context, as the other switches: a function-local static kept the FIRST call's value for the whole process)
+    const char *er = getenv("PRONTO_BATCH_REPLAY_ONELANE");
+    c->replay_onelane = er && er[0] == '1';
   }
   c->stride = ((long) batch + 63) / 64 * 64;
   c->nc = (n_states == 15) ? Lay<15>::NC : Lay<21>::NC;

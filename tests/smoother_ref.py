@@ -20,18 +20,28 @@ def start_of(w, zero_bias=False):
     return vec, quat, P0, q4
 
 
-def oracle_forward(oracle, w, n, T, B, zero_bias=False):
-    """Forward pass with the oracle, keeping (pred, filtered) posteriors of every step (INS update, then legodo)."""
-    vec, quat, P0, q4 = start_of(w, zero_bias)
-    v21, P21 = embed21(vec, P0)
-    ob = oracle.OracleBatch(v21, quat, P21)
+def oracle_forward(oracle, w, n, T, B, zero_bias=False, q4=None, cols=None, P0=None, corr=None):
+    """Forward pass with the oracle, keeping (pred, filtered) posteriors of every step (INS update, then legodo).
+    q4: another process noise than the workload's; cols: the filters `cols` of the workload alone; P0: another start covariance;
+    corr = (idx, ticks, z2 [n_ticks,m,B], R2, quat_meas2, mask2): a correction behind the pairs `ticks` -- "filtered" is then the
+    posterior of the LAST update of the step."""
+    vec, quat, P0_w, q4_w = start_of(w, zero_bias)
+    q4 = q4_w if q4 is None else q4
+    P0 = P0_w if P0 is None else P0
+    cols = np.arange(w.B) if cols is None else cols
+    v21, P21 = embed21(vec[:, cols], P0[:, :, cols])
+    ob = oracle.OracleBatch(v21, quat[:, cols], P21)
     hist = []
     for k in range(T):
-        imu = w.imu_block(k)
+        imu = np.ascontiguousarray(w.imu_block(k)[:, cols])
         lo, mask = w.legodo_block(k)
+        lo, mask = np.ascontiguousarray(lo[:, cols]), np.ascontiguousarray(mask[cols])
         ob.predict(imu, q4)
         pred = (ob.vec.copy(), ob.quat.copy(), ob.cov.copy())
         ob.update_indexed([3, 4, 5], lo[0:3], lo[3:6], mask=mask)
+        if corr is not None and k in corr[1]:
+            z2, R2, qm2, mask2 = (np.ascontiguousarray(a[list(corr[1]).index(k)][..., cols]) for a in corr[2:])
+            ob.update_indexed(corr[0], z2, R2, quat_meas=qm2, mask=mask2)
         hist.append((pred, (ob.vec.copy(), ob.quat.copy(), ob.cov.copy())))
     return hist
 
@@ -62,9 +72,10 @@ def oracle_smooth_step(oracle, nxt_pred, nxt, cur, dt):
     return out_v, out_q, out_P
 
 
-def oracle_backward_pass(oracle, w, n, T, B, dt, keep):
-    """Forward pass + full backward recursion with the oracle; returns {k: (vec, quat, cov)} for the steps in `keep`."""
-    hist = oracle_forward(oracle, w, n, T, B)
+def oracle_backward_pass(oracle, w, n, T, B, dt, keep, **forward):
+    """Forward pass + full backward recursion with the oracle; returns {k: (vec, quat, cov)} for the steps in `keep`.
+    forward: q4 / cols / P0 of oracle_forward."""
+    hist = oracle_forward(oracle, w, n, T, B, **forward)
     nxt = hist[T - 1][1]
     out = {}
     for k in range(T - 2, -1, -1):

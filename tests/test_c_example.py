@@ -38,6 +38,22 @@ def test_param_sweep_example_runs_on_gpu():
 
 
 @pytest.mark.gpu
+def test_param_sweep_example_in_the_cache_blocked_order_on_gpu():
+    """The example's batch is two whole tiles with a process noise per filter: forced into pb_run_legodo's cache-blocked order (two
+    blocks of 64) it must find the same best candidate with the same log-likelihood as step by step -- the second block steps with
+    ITS filters' noise."""
+    exe = build()
+    found = []
+    for blocked in ("0", "1"):
+        env = dict(os.environ, PRONTO_BATCH_BLOCKED=blocked, PRONTO_BATCH_BLOCK_FILTERS="64")
+        r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+        print(r.stdout, r.stderr)
+        assert r.returncode == 0 and "PASS" in r.stdout, r.stdout + r.stderr
+        found.append(r.stdout[r.stdout.index("best log-likelihood"):])
+    assert found[0] == found[1], found
+
+
+@pytest.mark.gpu
 def test_leg_sweep_example_runs_on_gpu():
     exe = build("leg_sweep")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)

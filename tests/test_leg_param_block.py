@@ -132,13 +132,17 @@ def test_open_loop_odometry_with_per_filter_thresholds_on_gpu(oracle, n):
 
 
 # ---- 2, 3. the pair kernels against the oracle chain -------------------------------------------------------------------------
-def pair_chain(oracle, n, kind, mode, B, blk, est=None):
+def pair_chain(oracle, n, kind, mode, B, blk, est=None, q_block=None, param_block=True, dense_p0=None):
     """test_pair_call_against_the_oracle_chain_on_gpu / ..._in_the_six_row_modes_... with a parameter block: per tick po_imu_process_step,
     then on the ORACLE filter's own pose after that step po_torque_adjust -> po_fk -> po_leg_update_wc of THAT filter's robot ->
     LegOdoCommon's measurement with THAT filter's noises -> po_indexed_update, the zero_initial_velocity counter per filter.  est = None:
     the oracle chain alone (what it yields must stay finite and reach the counts before a kernel is held against it).
+    q_block [4, B]: a process noise per filter (pb_set_process_noise_block), the oracle's process step made per filter; param_block =
+    False: blk is uniform_block(B) and the context gets its values as the scalars of pb_legodo_init and of the pair call; dense_p0: the
+    seed of a dense SPD matrix added to the start covariance (test_gpu_parity.make_pair's).
     -> (updates applied, three-row fall-backs, statuses seen, the oracle filter)"""
     import legs
+    from noise_block import oracle_noise_block, per_filter_oracle
     from util import embed21
     T, ZERO = 260, 4
     L = oracle.lib()
@@ -146,6 +150,9 @@ def pair_chain(oracle, n, kind, mode, B, blk, est=None):
     gain = np.array([7000, 10000, 10000, 10000, 10000, 10000] * 2, dtype=np.float32)
     w = Workload(B, n_states=n, dt_us=2000)
     vec, quat, P0 = w.initial_state()
+    if dense_p0:
+        from util import random_spd
+        P0 = P0 + random_spd(n, B, 0.03, dense_p0)
     v21, P21 = embed21(vec, P0)
     ob = oracle.OracleBatch(v21, quat, P21)
     orc = PerFilterLegs(oracle, blk)
@@ -161,7 +168,15 @@ def pair_chain(oracle, n, kind, mode, B, blk, est=None):
         est.legodo_set_zero_initial_velocity(ZERO)
         if mode:
             est.legodo_set_measurement_mode(mode, 7.0, 8.0, 9.0)   # (the three noises: replaced by the block)
-        est.legodo_set_param_block(blk)
+        r_call = (-1.0, -1.0)                                  # (the two noises: ignored with a block)
+        if param_block:
+            est.legodo_set_param_block(blk)
+        else:
+            assert mode == 0 and np.array_equal(blk, uniform_block(B))
+            r_call = R_VXYZ
+        if q_block is not None:
+            d_q = torch.from_numpy(np.ascontiguousarray(q_block)).to(dev)   # (alive until the last call below has been read back)
+            est.set_process_noise_block(d_q)
         lo = torch.zeros((6 if mode == 0 else 12, B), dtype=torch.float64, device=dev)
         mk = torch.zeros((2, B) if mode == 2 else (B,), dtype=torch.uint8, device=dev)
     bcast = kind.endswith("bcast")
@@ -186,13 +201,16 @@ def pair_chain(oracle, n, kind, mode, B, blk, est=None):
             if kind.startswith("joints"):
                 a = (np.ascontiguousarray(jp[:, 0]), np.ascontiguousarray(je[:, 0]), np.ascontiguousarray(forces[:, 0])) if bcast else \
                     tuple(torch.from_numpy(x).to(dev) for x in (jp, je, forces))
-                est.step_legodo_joints(imu_in, q4, utime, *a, -1.0, -1.0, lo, mk)   # (the two noises: ignored with a block)
+                est.step_legodo_joints(imu_in, q4, utime, *a, *r_call, lo, mk)
             else:
-                est.step_legodo_feet(imu_in, q4, utime, torch.from_numpy(ofeet).to(dev), torch.from_numpy(forces).to(dev), -1.0, -1.0, lo, mk)
+                est.step_legodo_feet(imu_in, q4, utime, torch.from_numpy(ofeet).to(dev), torch.from_numpy(forces).to(dev), *r_call, lo, mk)
             g_mask, g_lo = mk.cpu().numpy().reshape(-1, B), lo.cpu().numpy()
         if bcast:
             ofeet, forces = np.repeat(ofeet, B, axis=1), np.repeat(forces, B, axis=1)
-        ob.predict(imu, q4)
+        if q_block is None:
+            ob.predict(imu, q4)
+        else:
+            per_filter_oracle(ob, oracle_noise_block(q_block, n), lambda q: ob.predict(imu, q))
         od, os_, op = orc.update(utime, np.ascontiguousarray(ofeet), forces.astype(np.float64), np.ascontiguousarray(ob.quat),
                                  wpos=np.ascontiguousarray(ob.vec[9:12]) if mode == 2 else None)
         valid = os_ >= 0

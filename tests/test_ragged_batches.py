@@ -11,6 +11,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from noise_block import masked_oracle_step
 from util import pad_z, rel, rel_elem
 
 from pronto_amd.synth import Workload
@@ -228,14 +229,6 @@ def test_ins_body_block(config):
 STEP_B, STEP_T = 130, 40
 STEP_WAVE_IDLE, STEP_ALL_IDLE, STEP_ONE_SHOT = 7, 13, 20
 STEP_CHECKS = (0, 9, 39)          # steps 1, 10 and 40
-
-
-def masked_oracle_step(ob, valid, fn):
-    """fn() on every column of the oracle batch, then the columns without a message put back: their estimator did nothing"""
-    keep = [a.copy() for a in (ob.vec, ob.quat, ob.cov_cm, ob.ll)]
-    fn()
-    idle = np.asarray(valid) == 0
-    ob.vec[:, idle], ob.quat[:, idle], ob.cov_cm[:, :, idle], ob.ll[idle] = keep[0][:, idle], keep[1][:, idle], keep[2][:, :, idle], keep[3][idle]
 
 
 def _step_validity():
