@@ -4,6 +4,7 @@
 // The glue below mirrors k_step (rbis_step_kernels.hpp) / k_update_lane (rbis_update_kernels.hpp).
 #include <cstdint>
 #include <cstring>
+#include <type_traits>
 
 #include "../pronto_amd/csrc/rbis_device.hpp"
 
@@ -173,6 +174,96 @@ extern "C" void hh_step_coop_correct(int ns, int kind, int mode, double *st, lon
   else if (ns == 15) step_coop<15, CorrPosYaw>(st, stride, B, imu, lo, mask, q4, g, tol, mode, z2, rd2, qm2, mask2);
   else if (kind == 0) step_coop<21, CorrPosOrient>(st, stride, B, imu, lo, mask, q4, g, tol, mode, z2, rd2, qm2, mask2);
   else step_coop<21, CorrPosYaw>(st, stride, B, imu, lo, mask, q4, g, tol, mode, z2, rd2, qm2, mask2);
+}
+
+// every handler list as a stand-alone update on the two-role mapping (k_step_coop<NS, false, ., CORR>, pb_update_ct.hip); kind as
+// hh_update_quad.  Returns -1 for what the library does not build (21 states with six rows).
+extern "C" int hh_update_coop(int ns, int kind, double *st, long stride, int B, const double *z2, const double *rd2, const double *qm2,
+                              const uint8_t *mask2, double g, double tol)
+{
+  const double imu[7] = { 0, 0, 0, 0, 0, 0, 0 }, lo[6] = { 0, 0, 0, 1, 1, 1 }, q4[4] = { 0, 0, 0, 0 };
+  auto run = [&](auto corr) {
+    using CORR = decltype(corr);
+    if (ns == 21 && CORR::M > 4) return -1;
+    for (int b = 0; b < B; b++) {  // (one filter per call: the dummy IMU / leg-odometry blocks above are one filter wide)
+      const uint8_t mk = mask2 ? mask2[b] : 1;
+      double zz[6], rr[6], qq[4];
+      for (int i = 0; i < CORR::M; i++) { zz[i] = z2[i * B + b]; rr[i] = rd2[i * B + b]; }
+      for (int i = 0; i < 4; i++) qq[i] = qm2 ? qm2[i * B + b] : (i == 0);
+      if (ns == 15) step_coop<15, CORR>(st + b, stride, 1, imu, lo, nullptr, q4, g, tol, 2, zz, rr, qq, &mk);
+      else step_coop<21, CORR>(st + b, stride, 1, imu, lo, nullptr, q4, g, tol, 2, zz, rr, qq, &mk);
+    }
+    return 0;
+  };
+  switch (kind) {
+  case 0: return run(CorrVel{});
+  case 1: return run(CorrPos{});
+  case 2: return run(CorrPosVel{});
+  case 3: return run(CorrPosOrient{});
+  case 4: return run(CorrPosYaw{});
+  case 5: return run(CorrVelYaw{});
+  case 6: return run(CorrYaw{});
+  case 7: return run(CorrGpfYawPos{});
+  case 8: return run(CorrGpfChiPos{});
+  default: return run(CorrGpfZ{});
+  }
+}
+
+// the one-lane update with a run-time index list (k_update_lane_rt, rbis_update_kernels.hpp; k_update_lane gives the same bits for
+// the same list): R first, then P[idx, idx] added to it; the measured columns gathered; measurement_update_cols.
+// rkind 0: R [m][B] diagonal, 1: R [m*m][B] full column-major
+template <int NS, int M>
+static void update_rt(double *st, long stride, int B, const int *idx, const double *z, const double *R, int rkind, const double *qm,
+                      const uint8_t *mask, double g, double tol)
+{
+  Consts k{ g, tol };
+  for (int b = 0; b < B; b++) {
+    const bool upd = !mask || mask[b];
+    double x[NS], q[4], ll, P[Lay<NS>::NP];
+    load<NS>(st, stride, b, x, q, ll, P);
+    double dq[3] = { 0.0, 0.0, 0.0 };
+    if (qm) {
+      const double qmeas[4] = { qm[b], qm[B + b], qm[2 * B + b], qm[3 * B + b] };
+      subtract_quats(qmeas, q, dq);
+    }
+    double S[M * (M + 1) / 2], W[NS][M], resid[M];
+    for (int i = 0; i < M; i++)
+      for (int j = 0; j <= i; j++) {
+        const double r = rkind ? R[(j * M + i) * B + b] : (i == j ? R[i * B + b] : 0.0);
+        S[pk(i, j)] = upd ? r : (i == j ? 1.0 : 0.0);
+      }
+    for (int kk = 0; kk < M; kk++) {
+      const int c = idx[kk];
+      for (int i = 0; i < NS; i++) W[i][kk] = P[pk(i, c)];
+      double r = z[kk * B + b] - x[c];
+      if (qm && c >= 6 && c <= 8) r = dq[c - 6];
+      resid[kk] = upd ? r : 0.0;
+      for (int j = 0; j < kk; j++) S[pk(kk, j)] += W[c][j];
+      S[pk(kk, kk)] += P[pk(c, c)];
+    }
+    measurement_update_cols<NS, M>(x, q, P, ll, resid, S, W, k, NoSink(), upd);
+    store<NS>(st, stride, b, x, q, ll, P);
+  }
+}
+
+extern "C" int hh_update_rt(int ns, int m, const int *idx, double *st, long stride, int B, const double *z, const double *R, int rkind,
+                            const double *qm, const uint8_t *mask, double g, double tol)
+{
+  auto run = [&](auto mm) {
+    constexpr int M = decltype(mm)::value;
+    if (ns == 15) update_rt<15, M>(st, stride, B, idx, z, R, rkind, qm, mask, g, tol);
+    else update_rt<21, M>(st, stride, B, idx, z, R, rkind, qm, mask, g, tol);
+    return 0;
+  };
+  switch (m) {
+  case 1: return run(std::integral_constant<int, 1>{});
+  case 2: return run(std::integral_constant<int, 2>{});
+  case 3: return run(std::integral_constant<int, 3>{});
+  case 4: return run(std::integral_constant<int, 4>{});
+  case 5: return run(std::integral_constant<int, 5>{});
+  case 6: return run(std::integral_constant<int, 6>{});
+  default: return -1;
+  }
 }
 
 // ---- LegOdoCommon's six-row measurements inside the step (SIX, rbis_coop.hpp): the two roles as two threads with a real
