@@ -215,15 +215,35 @@ public:
   }
 };
 
+// The de-duplication rule of imu_stream.cpp:62-98 on plain numbers, one state per packet stream: IMUStream below uses it for one
+// robot's messages, the segment replayers' KVH decoder (segment_channels.hpp) keeps one per log segment.
+struct IMUStreamRule {
+  int64_t last_packet = -1, last_packet_utime = 0;
+  // in front of a message's packets: a newest packet count that went backwards is a time skip and resets the stream (:63-68)
+  bool resetIfBackwards(int64_t newest_packet_count)
+  {
+    if (newest_packet_count >= last_packet) return false;
+    last_packet = -1;
+    last_packet_utime = 0;
+    return true;
+  }
+  // per packet, oldest first: true = new (a packet count above the last one seen), with its time behind the last accepted packet's
+  bool accept(int64_t packet_count, int64_t utime, int64_t &utime_delta)
+  {
+    if (packet_count <= last_packet) return false;
+    utime_delta = utime - last_packet_utime;
+    last_packet = packet_count;
+    last_packet_utime = utime;
+    return true;
+  }
+};
+
 class IMUStream {
 public:
-  IMUStream() : last_packet_(-1), last_packet_utime_(0), counter_(0) {}
   IMUBatch convertFromLCMBatch(const msgs::kvh_raw_imu_batch_t *msg)
   {
-    if (!msg->raw_imu.empty() && msg->raw_imu[0].packet_count < last_packet_) {
+    if (!msg->raw_imu.empty() && rule_.resetIfBackwards(msg->raw_imu[0].packet_count)) {
       fprintf(stdout, "Detected time skip, resetting IMUStream\n");  // imu_stream.cpp:63-68
-      last_packet_ = -1;
-      last_packet_utime_ = 0;
       counter_ = 0;
     }
     IMUBatch batch;
@@ -237,11 +257,8 @@ public:
       raw.packet_count = m.packet_count;
       raw.delta_rotation = m.delta_rotation;
       raw.linear_acceleration = m.linear_acceleration;
-      if (m.packet_count > last_packet_) {
-        raw.utime_delta = m.utime - last_packet_utime_;
+      if (rule_.accept(m.packet_count, m.utime, raw.utime_delta)) {
         batch.packets.push_back(raw);
-        last_packet_ = m.packet_count;
-        last_packet_utime_ = m.utime;
       } else {
         raw.utime_delta = m.utime - (-m.utime);  // "deliberately obfuscate the delta field" (:87-88)
         batch.packets_old.push_back(raw);
@@ -253,8 +270,8 @@ public:
   int getNumberBatchSinceReset() const { return counter_; }
 
 private:
-  int64_t last_packet_, last_packet_utime_;
-  int counter_;
+  IMUStreamRule rule_;
+  int counter_ = 0;
 };
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -46,7 +46,7 @@
 #include <chrono>
 #include <deque>
 
-#include "mav_state_est_batch.hpp"
+#include "segment_channels.hpp"
 
 namespace MavStateEst {
 
@@ -69,10 +69,7 @@ public:
   Stats stats;
   size_t readahead_cap = 4096;
 
-  explicit SegmentBatcher(MavStateEstimator *est)
-      : est_(est), B_(est->B), final_vec_((size_t) est->n * est->B, 0.0), final_quat_((size_t) 4 * est->B, 0.0),
-        final_cov_((size_t) est->n * est->n * est->B, 0.0), final_ll_((size_t) est->B, 0.0), final_utime_((size_t) est->B, 0),
-        finished_((size_t) est->B, 0) {}
+  explicit SegmentBatcher(MavStateEstimator *est) : est_(est), B_(est->B), results_(est->n, est->B) {}
   ~SegmentBatcher()
   {
     est_->flushPending();   // (an update the estimator is holding back may still read the device blocks)
@@ -169,159 +166,82 @@ public:
   }
 
   // ---- typed subscriptions: channel -> the callback FrontEnd::addSensor returned ----
+  // What a channel reads of its wire type and the record it is decoded into are segment_channels.hpp's; here the records of a batched message's
+  // columns are scattered into the channel's page-locked block.  A column without a message keeps what the block held, masked -- except where noted.
   // bot_core::ins_t by field name (utime, gyro[3], accel[3]): InsHandler::processMessage
   void subscribeIns(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                     std::function<void(const msgs::ins_t *)> cb)
   {
+    typedef segment_channels::InsChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentBatcher");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "gyro", "accel" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentBatcher: %s has no utime / gyro / accel members\n", type.c_str());
-    c.decode = [plan](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->run(ev.data.data(), ev.data.size(), x, st.shape, nullptr) || x[0].num.size() != 1 || x[1].num.size() != 3 || x[2].num.size() != 3) return false;
-      r.utime = (int64_t) x[0].num[0];
-      r.d.assign(x[1].num.begin(), x[1].num.end());
-      r.d.insert(r.d.end(), x[2].num.begin(), x[2].num.end());
-      return true;
-    };
-    double *blk = pinned<double>((size_t) 6 * B_);
-    uint8_t *valid = pinned<uint8_t>((size_t) B_);
-    auto last = std::make_shared<std::vector<double>>((size_t) 6 * B_, 0.0);
-    c.dispatch = [this, cb, blk, valid, last](const std::vector<const Rec *> &col, int64_t utime) {
+    c.decode = record_decoder(ch, C::BYTES);
+    uint8_t *blk = block(C::BYTES);
+    c.dispatch = [this, cb, blk](const std::vector<const Rec *> &col, int64_t utime) {
+      uint8_t *valid = rows<uint8_t>(blk, C::VALID);
       PB_SHIM_PARALLEL_FOR
       for (int s = 0; s < B_; s++) {
-        valid[s] = col[(size_t) s] != nullptr;
-        for (int i = 0; i < 6; i++) {
-          if (col[(size_t) s]) (*last)[(size_t) i * B_ + s] = col[(size_t) s]->d[(size_t) i];
-          blk[(size_t) i * B_ + s] = (*last)[(size_t) i * B_ + s];   // (a filter without a message idles on its own last sample)
-        }
+        const Rec *r = col[(size_t) s];
+        valid[s] = r != nullptr;
+        if (r) put<double>(blk, C::GYRO, 6, r->bytes.data(), s);   // (a filter without a message idles on its own last sample)
       }
-      msgs::ins_t m{ utime, BatchArray(blk, PB_HOST), BatchArray(blk + (size_t) 3 * B_, PB_HOST) };
-      m.valid = valid;
+      const msgs::ins_t m = C::message(utime, blk, (size_t) B_, PB_HOST);
       keep_imu_tick(col, valid, utime);
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::kvh_raw_imu_batch_t (utime, raw_imu[]{utime, packet_count, delta_rotation[3], linear_acceleration[3]}; raw_imu[0] is the
-  // NEWEST packet): the reference's Atlas IMU channel (fusion.cpp:161-163 -> InsHandler::processMessageAtlas, sensor_handlers.cpp:165-252)
-  // for N independent logs -> InsHandler::processMessageAtlasSegments.  Every segment has its OWN IMUStream de-duplication state
-  // (imu_stream.cpp:62-98); atlas_filter = the handler's (true: the new packets go to the device notch cascade with per-filter
-  // counts; false: newest packet, raw_dt from the two newest); max_packets = the most packets a message can carry.
-  // (SegmentStreamer has the same subscription with the blocks already in HBM.)
+  // bot_core::kvh_raw_imu_batch_t: the reference's Atlas IMU channel (fusion.cpp:161-163 -> InsHandler::processMessageAtlas,
+  // sensor_handlers.cpp:165-252) for N independent logs -> InsHandler::processMessageAtlasSegments.  atlas_filter = the handler's;
+  // max_packets = rows of the new-packet block (more NEW packets than that are clamped).  A column without a message has utimes = 0.
   void subscribeKvhBatch(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type, bool atlas_filter, int max_packets,
                          std::function<void(const msgs::kvh_raw_imu_segments_t *)> cb)
   {
+    typedef segment_channels::KvhChannel C;
+    auto ch = std::make_shared<C>(schema, type, atlas_filter, max_packets, "SegmentBatcher");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(
-        schema->compile(type, { "utime", "raw_imu.utime", "raw_imu.packet_count", "raw_imu.delta_rotation", "raw_imu.linear_acceleration" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentBatcher: %s is not a kvh_raw_imu_batch_t\n", type.c_str());
-    const int MP = max_packets < 1 ? 1 : max_packets;
-    // Rec: utime; aux = number of new packets; d = new accelerations [3 * n_new] (oldest first, at most MP), delta_rotation [3], raw_dt
-    c.decode = [plan, MP, atlas_filter](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->run(ev.data.data(), ev.data.size(), x, st.shape, nullptr) || x[0].num.size() != 1) return false;
-      const size_t np = x[1].num.size();
-      if (np < 1 || x[2].num.size() != np || x[3].num.size() != 3 * np || x[4].num.size() != 3 * np) return false;
-      r.utime = (int64_t) x[0].num[0];
-      r.d.clear();
-      double drot[3] = { 0, 0, 0 }, raw_dt = 0;
-      int n_new = 0;
-      if (!atlas_filter) {   // sensor_handlers.cpp:199-204
-        if (np < 2) return false;
-        for (int i = 0; i < 3; i++) { r.d.push_back(x[4].num[(size_t) i]); drot[i] = x[3].num[(size_t) i]; }
-        raw_dt = (double) ((int64_t) x[1].num[0] - (int64_t) x[1].num[1]) * 1E-6;
-        n_new = 1;
-      } else {               // IMUStream::convertFromLCMBatch, this segment's own state
-        if ((int64_t) x[2].num[0] < st.last_packet) { st.last_packet = -1; st.last_packet_utime = 0; }
-        for (size_t i = np; i-- > 0;) {
-          const int64_t cnt = (int64_t) x[2].num[i], put = (int64_t) x[1].num[i];
-          if (cnt <= st.last_packet) continue;
-          if (n_new < MP)
-            for (int a = 0; a < 3; a++) r.d.push_back(x[4].num[3 * i + (size_t) a]);
-          n_new++;
-          for (int a = 0; a < 3; a++) drot[a] = x[3].num[3 * i + (size_t) a];
-          raw_dt = (double) (put - st.last_packet_utime) * 1E-6;
-          st.last_packet = cnt;
-          st.last_packet_utime = put;
-        }
-        if (n_new > MP) n_new = MP;
-      }
-      r.aux = n_new;
-      r.d.resize((size_t) 3 * n_new);
-      r.d.insert(r.d.end(), drot, drot + 3);
-      r.d.push_back(raw_dt);
-      return true;
-    };
-    double *acc = pinned<double>((size_t) 3 * MP * B_), *drot = pinned<double>((size_t) 3 * B_), *raw_dt = pinned<double>((size_t) B_);
-    int64_t *ut = pinned<int64_t>((size_t) B_);
-    int32_t *n_new = pinned<int32_t>((size_t) B_);
-    uint8_t *valid = pinned<uint8_t>((size_t) B_);
-    std::fill_n(acc, (size_t) 3 * MP * B_, 0.0);
-    std::fill_n(drot, (size_t) 3 * B_, 0.0);
-    std::fill_n(raw_dt, (size_t) B_, 1.0);
-    c.dispatch = [this, cb, MP, acc, drot, raw_dt, ut, n_new, valid](const std::vector<const Rec *> &col, int64_t utime) {
+    c.decode = record_decoder(ch, ch->BYTES);
+    uint8_t *blk = block(ch->BYTES);
+    std::fill_n(rows<double>(blk, ch->RAW_DT), (size_t) B_, 1.0);
+    c.dispatch = [this, cb, ch, blk](const std::vector<const Rec *> &col, int64_t utime) {
+      int32_t *n_new = rows<int32_t>(blk, ch->N_NEW);
+      uint8_t *valid = rows<uint8_t>(blk, ch->VALID);
+      int64_t *ut = rows<int64_t>(blk, ch->UTIME);
       PB_SHIM_PARALLEL_FOR
       for (int s = 0; s < B_; s++) {
         const Rec *r = col[(size_t) s];
-        const int nn = r ? (int) r->aux : 0;
+        const int nn = r ? (int) *segment_channels::member<int32_t>(r->bytes.data(), ch->N_NEW) : 0;
         n_new[s] = nn;
         valid[s] = nn > 0;
         ut[s] = r ? r->utime : 0;
         if (nn <= 0) continue;   // (no message, or no new packet: the filter idles; its arrays keep their last values)
-        for (int p = 0; p < nn; p++)
-          for (int a = 0; a < 3; a++) acc[((size_t) p * 3 + (size_t) a) * B_ + s] = r->d[(size_t) 3 * p + (size_t) a];
-        for (int a = 0; a < 3; a++) drot[(size_t) a * B_ + s] = r->d[(size_t) 3 * nn + (size_t) a];
-        raw_dt[s] = r->d[(size_t) 3 * nn + 3];
+        put<double>(blk, ch->ACCEL, (size_t) 3 * nn, r->bytes.data(), s);
+        put<double>(blk, ch->DELTA_ROTATION, 3, r->bytes.data(), s);
+        put<double>(blk, ch->RAW_DT, 1, r->bytes.data(), s);
       }
-      msgs::kvh_raw_imu_segments_t m;
-      m.utime = utime;
-      m.max_new = MP;
-      m.n_new = n_new;
-      m.valid = valid;
-      m.new_accel = acc;
-      m.delta_rotation = drot;
-      m.raw_dt = raw_dt;
-      m.utimes = ut;
-      m.mem = PB_HOST;
+      const msgs::kvh_raw_imu_segments_t m = ch->message(utime, blk, (size_t) B_, PB_HOST);
       keep_imu_tick(col, valid, utime);
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::joint_state_t (utime, joint_name[], joint_position[], joint_velocity[], joint_effort[]): LegOdoHandler::processMessage
+  // bot_core::joint_state_t (utime, joint_name[], joint_position[], joint_velocity[], joint_effort[]): LegOdoHandler::processMessage.
+  // Every segment's list is held to the LEAD's of the same batched message; a column with another list is masked and counted as undecodable.
   void subscribeJointState(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                            std::function<void(const msgs::joint_state_t *)> cb)
   {
+    typedef segment_channels::JointStateChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentBatcher");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(
-        schema->compile(type, { "utime", "joint_name", "joint_position", "joint_velocity", "joint_effort" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentBatcher: %s is not a joint_state_t\n", type.c_str());
-    c.decode = [plan](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      bool same = false;
-      if (!plan->run(ev.data.data(), ev.data.size(), x, st.shape, &same) || x[0].num.size() != 1) return false;
-      if (!same || !st.names) {   // a new joint list (normally: the first message of the segment)
-        st.names = std::make_shared<const std::vector<std::string>>(x[1].str);
-        uint64_t h = 1469598103934665603ull;   // FNV-1a over the names and their boundaries
-        for (const std::string &nm : *st.names) {
-          for (unsigned char ch : nm) h = (h ^ ch) * 1099511628211ull;
-          h = (h ^ 0xffu) * 1099511628211ull;
-        }
-        st.names_hash = h;
-      }
-      const size_t n = st.names->size();
-      if (x[2].num.size() != n || x[3].num.size() != n || x[4].num.size() != n) return false;
-      r.utime = (int64_t) x[0].num[0];
+    c.decode = [ch](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
+      const std::vector<std::string> *fresh = nullptr;
+      if (!ch->open(ev.data.data(), ev.data.size(), st, &fresh)) return false;
+      if (fresh) st.names = std::make_shared<const std::vector<std::string>>(*fresh);   // a new joint list (normally: the first message of the segment)
+      const C::Layout lay(st.names->size());
+      r.bytes.resize(lay.BYTES);
       r.names = st.names;
       r.names_hash = st.names_hash;
-      r.f.resize(3 * n);
-      for (size_t j = 0; j < n; j++) {
-        r.f[j] = (float) x[2].num[j];
-        r.f[n + j] = (float) x[3].num[j];
-        r.f[2 * n + j] = (float) x[4].num[j];
-      }
-      return true;
+      return ch->read(ev.data.data(), st, lay, r.bytes.data(), r.utime);
     };
     auto st = std::make_shared<JointBlocks>();
     c.dispatch = [this, cb, st](const std::vector<const Rec *> &col, int64_t utime) {
@@ -329,22 +249,21 @@ public:
       for (const Rec *r : col)
         if (r) { lead = r; break; }
       if (lead == nullptr) return;
-      const size_t n = lead->names->size();
-      if (st->rows != n) {   // first message (or a new joint list): size the page-locked blocks
+      const size_t n = lead->names->size(), B = (size_t) B_;
+      const C::Layout lay(n);
+      if (st->rows != n || st->blk == nullptr) {   // first message (or a new joint list): size the page-locked block and its float part in HBM
         st->rows = n;
-        st->jp = pinned<float>(3 * n * (size_t) B_);
-        st->ut = pinned<int64_t>((size_t) B_);
-        st->valid = pinned<uint8_t>((size_t) B_);
-        std::fill_n(st->jp, 3 * n * (size_t) B_, 0.0f);
+        st->blk = block(lay.BYTES);
         void *d = nullptr;
-        if (pb_malloc(est_->ctx, sizeof(float) * 3 * n * (size_t) B_, &d) != PB_OK) {
+        if (pb_malloc(est_->ctx, sizeof(float) * 3 * n * B, &d) != PB_OK) {
           fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
           exit(1);
         }
         st->d_jp = (float *) d;
         device_.push_back(d);
       }
-      float *jp = st->jp, *jv = jp + n * (size_t) B_, *je = jv + n * (size_t) B_;
+      uint8_t *blk = st->blk, *valid = rows<uint8_t>(blk, lay.VALID);
+      int64_t *ut = rows<int64_t>(blk, lay.UTIME);
       int64_t mismatched = 0;
       PB_SHIM_PARALLEL_FOR_SUM(mismatched)
       for (int s = 0; s < B_; s++) {
@@ -353,14 +272,9 @@ public:
         // list was decoded: 30 string compares per segment and message were a third of this loop)
         const bool ok = r != nullptr && r->names_hash == lead->names_hash && r->names->size() == n;
         if (r != nullptr && !ok) mismatched++;
-        st->valid[s] = ok;
-        st->ut[s] = ok ? r->utime : 0;
-        if (!ok) continue;                                         // (the block keeps this filter's last message; it is masked)
-        for (size_t j = 0; j < n; j++) {
-          jp[j * B_ + s] = r->f[j];
-          jv[j * B_ + s] = r->f[n + j];
-          je[j * B_ + s] = r->f[2 * n + j];
-        }
+        valid[s] = ok;
+        ut[s] = ok ? r->utime : 0;
+        if (ok) put<float>(blk, lay.POSITION, 3 * n, r->bytes.data(), s);   // (else the block keeps this filter's last message; it is masked)
       }
       stats.undecodable += mismatched;
       // The joint block goes to HBM here (one DMA from page-locked memory) and the handler gets a DEVICE message: with the IMU
@@ -370,112 +284,83 @@ public:
       // device takes 25: a copy on a second stream into alternating blocks, waiting for nothing but itself, took the same -- the
       // device idles between ticks in this host-bound replay and every burst pays its wake-up.)
       int urc = PB_OK;
-      timed(stats.t_upload, [&]() { urc = pb_memcpy_h2d(est_->ctx, st->d_jp, jp, sizeof(float) * 3 * n * (size_t) B_); });
+      timed(stats.t_upload, [&]() { urc = pb_memcpy_h2d(est_->ctx, st->d_jp, rows<float>(blk, lay.POSITION), sizeof(float) * 3 * n * B); });
       if (urc != PB_OK) {
         fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
         return;
       }
-      msgs::joint_state_t m;
-      m.utime = utime;
-      m.joint_name = *lead->names;
-      m.joint_position = st->d_jp;
-      m.joint_velocity = st->d_jp + n * (size_t) B_;
-      m.joint_effort = st->d_jp + 2 * n * (size_t) B_;
-      m.mem = PB_DEVICE;
-      m.utimes = st->ut;
-      m.valid = st->valid;
+      const msgs::joint_state_t m = C::message(utime, *lead->names, lay, B, st->d_jp, PB_DEVICE, blk, PB_HOST);
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::six_axis_force_torque_array_t (sensors[].force[3]; sensors 0 / 1 = left / right foot): LegOdoHandler::forceTorqueHandler
+  // bot_core::six_axis_force_torque_array_t (sensors[].force[3]; sensors 0 / 1 = left / right foot): LegOdoHandler::forceTorqueHandler,
+  // with the signed force z of the two feet as doubles, [2][B]
   void subscribeForceTorque(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                             std::function<void(const msgs::six_axis_force_torque_array_t *)> cb)
   {
+    auto ch = std::make_shared<segment_channels::ForceTorqueChannel>(schema, type, "SegmentBatcher");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "sensors.force" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentBatcher: %s is not a six_axis_force_torque_array_t\n", type.c_str());
-    c.decode = [plan](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->run(ev.data.data(), ev.data.size(), x, st.shape, nullptr) || x[0].num.size() != 1 || x[1].num.size() < 6) return false;
-      r.utime = (int64_t) x[0].num[0];
-      r.d = { x[1].num[2], x[1].num[5] };   // sensors[0].force[2], sensors[1].force[2]
-      return true;
+    c.decode = [ch](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
+      r.bytes.resize(2 * sizeof(double));
+      return ch->decode(ev.data.data(), ev.data.size(), st, (double *) r.bytes.data(), r.utime);
     };
-    double *fz = pinned<double>((size_t) 2 * B_);
-    std::fill_n(fz, (size_t) 2 * B_, 0.0);
-    c.dispatch = [this, cb, fz](const std::vector<const Rec *> &col, int64_t utime) {
+    uint8_t *blk = block(2 * sizeof(double));
+    c.dispatch = [this, cb, blk](const std::vector<const Rec *> &col, int64_t utime) {
       PB_SHIM_PARALLEL_FOR
       for (int s = 0; s < B_; s++)
-        if (col[(size_t) s]) {   // (the handler keeps the LAST force/torque message, per filter: a missing one changes nothing)
-          fz[s] = col[(size_t) s]->d[0];
-          fz[(size_t) B_ + s] = col[(size_t) s]->d[1];
-        }
-      msgs::six_axis_force_torque_array_t m{ utime, BatchArray(fz, PB_HOST) };
+        if (col[(size_t) s]) put<double>(blk, 0, 2, col[(size_t) s]->bytes.data(), s);   // (the handler keeps the LAST force/torque message, per filter: a missing one changes nothing)
+      msgs::six_axis_force_torque_array_t m{ utime, BatchArray((const double *) blk, PB_HOST) };
       timed(stats.t_handler, [&]() { cb(&m); });
     };
     chans_[channel] = std::move(c);
   }
-  // pronto::update_t (pronto_wire.hpp): FovisHandler::processMessage.  timestamp / prev_timestamp are the lead's.
+  // pronto::update_t (pronto_wire.hpp): FovisHandler::processMessage.  timestamp / prev_timestamp are the lead's.  A column without a
+  // message is blank.
   void subscribeUpdate(const std::string &channel, std::function<void(const msgs::update_t *)> cb)
   {
+    typedef segment_channels::UpdateChannel C;
     Chan c;
     c.decode = [](const pronto_wire::LogEvent &ev, Rec &r, Stream &) {
-      pronto_wire::update_t w;
-      if (w.decode(ev.data.data(), ev.data.size()) < 0) return false;
-      r.utime = w.timestamp;
-      r.aux = w.prev_timestamp;
-      r.flag = w.estimate_status == pronto_wire::update_t::ESTIMATE_VALID;
-      r.d.assign(w.translation, w.translation + 3);
-      r.d.insert(r.d.end(), w.rotation, w.rotation + 4);
-      return true;
+      r.bytes.resize(C::BYTES);
+      return C::decode(ev.data.data(), ev.data.size(), r.bytes.data(), r.utime, &r.prev_behind);
     };
-    double *blk = pinned<double>((size_t) 7 * B_);
-    uint8_t *valid = pinned<uint8_t>((size_t) B_);
-    c.dispatch = [this, cb, blk, valid](const std::vector<const Rec *> &col, int64_t utime) {
+    uint8_t *blk = block(C::BYTES);
+    c.dispatch = [this, cb, blk](const std::vector<const Rec *> &col, int64_t utime) {
+      uint8_t none[C::BYTES];
+      C::blank(none);
       const Rec *lead = nullptr;
       for (int s = 0; s < B_; s++) {
         const Rec *r = col[(size_t) s];
         if (r && !lead) lead = r;
-        valid[s] = r != nullptr && r->flag;
-        for (int i = 0; i < 7; i++) blk[(size_t) i * B_ + s] = r ? r->d[(size_t) i] : (i == 3 ? 1.0 : 0.0);
+        put<double>(blk, C::TRANSLATION, 7, r ? r->bytes.data() : none, s);
+        put<uint8_t>(blk, C::VALID, 1, r ? r->bytes.data() : none, s);
       }
       if (lead == nullptr) return;
-      // (prev_timestamp on the batch's time base, like timestamp)
-      msgs::update_t m{ utime, lead->aux + (utime - lead->utime), valid, BatchArray(blk, PB_HOST), BatchArray(blk + (size_t) 3 * B_, PB_HOST) };
+      const msgs::update_t m = C::message(utime, lead->prev_behind, blk, (size_t) B_);
       cb(&m);
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::pose_t (utime, pos[3], vel[3], orientation[4]): ScanMatcherHandler::processMessage
+  // bot_core::pose_t (utime, pos[3], vel[3], orientation[4]): ScanMatcherHandler::processMessage.  A column without a message is blank.
   void subscribePose(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                      std::function<void(const msgs::pose_t *)> cb)
   {
+    typedef segment_channels::PoseChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentBatcher");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "pos", "vel", "orientation" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentBatcher: %s is not a pose_t\n", type.c_str());
-    c.decode = [plan](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->run(ev.data.data(), ev.data.size(), x, st.shape, nullptr) || x[0].num.size() != 1 || x[1].num.size() != 3 || x[2].num.size() != 3 ||
-          x[3].num.size() != 4)
-        return false;
-      r.utime = (int64_t) x[0].num[0];
-      r.d.assign(x[1].num.begin(), x[1].num.end());
-      r.d.insert(r.d.end(), x[2].num.begin(), x[2].num.end());
-      r.d.insert(r.d.end(), x[3].num.begin(), x[3].num.end());
-      return true;
-    };
-    double *blk = pinned<double>((size_t) 10 * B_);
-    uint8_t *valid = pinned<uint8_t>((size_t) B_);
-    c.dispatch = [this, cb, blk, valid](const std::vector<const Rec *> &col, int64_t utime) {
+    c.decode = record_decoder(ch, C::BYTES);
+    uint8_t *blk = block(C::BYTES);
+    c.dispatch = [this, cb, blk](const std::vector<const Rec *> &col, int64_t utime) {
+      uint8_t none[C::BYTES];
+      C::blank(none);
       PB_SHIM_PARALLEL_FOR
       for (int s = 0; s < B_; s++) {
-        const Rec *r = col[(size_t) s];
-        valid[s] = r != nullptr;
-        for (int i = 0; i < 10; i++) blk[(size_t) i * B_ + s] = r ? r->d[(size_t) i] : (i == 6 ? 1.0 : 0.0);
+        const uint8_t *rec = col[(size_t) s] ? col[(size_t) s]->bytes.data() : none;
+        put<double>(blk, C::POS, 10, rec, s);
+        put<uint8_t>(blk, C::VALID, 1, rec, s);
       }
-      msgs::pose_t m{ utime, BatchArray(blk, PB_HOST), BatchArray(blk + (size_t) 3 * B_, PB_HOST), BatchArray(blk + (size_t) 6 * B_, PB_HOST) };
-      m.valid = valid;
+      const msgs::pose_t m = C::message(utime, blk, (size_t) B_);
       cb(&m);
     };
     chans_[channel] = std::move(c);
@@ -556,11 +441,11 @@ public:
       // segments whose log has no subscribed event left: their run is complete, keep its result.  (fill() is also the read-ahead
       // of the next message: in parallel over the segments)
       PB_SHIM_PARALLEL_FOR
-      for (int s = 0; s < nseg; s++) got_[(size_t) s] = finished_[(size_t) s] || fill(*segs_[(size_t) s]);
+      for (int s = 0; s < nseg; s++) got_[(size_t) s] = results_.finished(s) || fill(*segs_[(size_t) s]);
       lap(tick, stats.t_fill);
       int first = -1;
       for (int s = 0; s <= nseg; s++) {
-        const bool ended = s < nseg && !finished_[(size_t) s] && !got_[(size_t) s];
+        const bool ended = s < nseg && !results_.finished(s) && !got_[(size_t) s];
         if (ended && first < 0) first = s;
         if (!ended && first >= 0) {
           finalize(first, s - first);
@@ -579,34 +464,20 @@ public:
   }
 
   // the head of every segment's filter at the end of ITS log (valid after run(); columns of segments never added are zero)
-  void finalState(RBIS &state, RBIM &cov) const
-  {
-    state = RBIS(est_->n, B_);
-    cov = RBIM(est_->n, B_);
-    state.vec = final_vec_;
-    state.quat = final_quat_;
-    cov.m = final_cov_;
-  }
-  const std::vector<double> &finalLogLikelihood() const { return final_ll_; }
-  int64_t finalUtime(int s) const { return final_utime_[(size_t) s]; }   // batch-level time at which segment s ended
+  void finalState(RBIS &state, RBIM &cov) const { results_.finalState(state, cov); }
+  const std::vector<double> &finalLogLikelihood() const { return results_.finalLogLikelihood(); }
+  int64_t finalUtime(int s) const { return results_.finalUtime(s); }   // batch-level time at which segment s ended
 
 private:
-  // one decoded message, in the compact form its channel's assembler reads
-  struct Rec {
-    int64_t utime = 0, aux = 0;
-    bool flag = false;
-    std::vector<double> d;
-    std::vector<float> f;
-    std::shared_ptr<const std::vector<std::string>> names;   // (shared by the messages of one stream: a joint list is decoded once)
-    uint64_t names_hash = 0;
-  };
-  // what one segment remembers about one channel between messages: the byte layout of its last message (Schema::Plan::Shape: a
-  // recorded stream repeats it, and the wanted numbers are then read by offset) and the strings that came with it
-  struct Stream {
-    pronto_wire::Schema::Plan::Shape shape;
+  struct Stream : segment_channels::ChannelState {   // what one segment remembers about one channel ... and the joint list itself
     std::shared_ptr<const std::vector<std::string>> names;
+  };
+  // one decoded message: its time and its channel's record (segment_channels.hpp)
+  struct Rec {
+    int64_t utime = 0, prev_behind = 0;   // (update_t: prev_timestamp - timestamp)
+    std::vector<uint8_t> bytes;
+    std::shared_ptr<const std::vector<std::string>> names;   // joint state: shared by the messages of one stream, a joint list is decoded once
     uint64_t names_hash = 0;
-    int64_t last_packet = -1, last_packet_utime = 0;   // IMUStream (imu_stream.hpp:10-37), one per segment
   };
   struct Chan {
     std::function<bool(const pronto_wire::LogEvent &, Rec &, Stream &)> decode;
@@ -615,9 +486,8 @@ private:
   };
   struct JointBlocks {
     size_t rows = 0;
-    float *jp = nullptr, *d_jp = nullptr;   // page-locked assembly block and its copy in HBM
-    int64_t *ut = nullptr;
-    uint8_t *valid = nullptr;
+    uint8_t *blk = nullptr;   // page-locked assembly block ...
+    float *d_jp = nullptr;    // ... and the copy of its float part in HBM
   };
   struct Seg {
     pronto_wire::LogReader rd;
@@ -683,12 +553,11 @@ private:
     imu_valid_.insert(imu_valid_.end(), valid, valid + B_);
     for (int s = 0; s < B_; s++) imu_utime_.push_back(col[(size_t) s] ? col[(size_t) s]->utime : 0);
   }
-  // the runs of segments [first, first + count) are complete: read their heads (applies whatever the estimator holds back first)
+  // the runs of segments [first, first + count) are complete: keep their results (applies whatever the estimator holds back first)
   void finalize(int first, int count)
   {
-    const int n = est_->n;
-    est_->flushPending();
     if (terminal_ >= 0) {   // smoothing: their posteriors at the end of their own logs, kept on the device (the newest step's "next")
+      est_->flushPending();
       ending_.assign((size_t) B_, 0);
       std::fill_n(ending_.begin() + first, count, (uint8_t) 1);
       if (pb_slot_select(est_->ctx, terminal_, PB_SLOT_HEAD, ending_.data(), 1, PB_HOST) != PB_OK) {
@@ -696,20 +565,31 @@ private:
         terminal_failed_ = true;   // (smooth() refuses: the terminal slot does not hold these segments' results)
       }
     }
-    std::vector<double> v((size_t) n * count), q((size_t) 4 * count), c((size_t) n * n * count), l((size_t) count);
-    if (pb_get_head(est_->ctx, first, count, v.data(), q.data(), c.data(), l.data(), PB_HOST) != PB_OK) {
-      fprintf(stderr, "SegmentBatcher: %s\n", pb_last_error(est_->ctx));
-      return;
-    }
-    for (int k = 0; k < count; k++) {
-      const size_t s = (size_t) (first + k);
-      for (int i = 0; i < n; i++) final_vec_[(size_t) i * B_ + s] = v[(size_t) i * count + k];
-      for (int i = 0; i < 4; i++) final_quat_[(size_t) i * B_ + s] = q[(size_t) i * count + k];
-      for (int i = 0; i < n * n; i++) final_cov_[(size_t) i * B_ + s] = c[(size_t) i * count + k];
-      final_ll_[s] = l[(size_t) k];
-      final_utime_[s] = est_->head_utime;
-      finished_[s] = 1;
-    }
+    results_.finalize(est_, first, count, "SegmentBatcher");
+  }
+  // column s of a block's member at record offset `off` (`count` elements of T) <- the same member of a record
+  template <class T>
+  void put(uint8_t *blk, size_t off, size_t count, const uint8_t *rec, int s) const
+  {
+    T *dst = rows<T>(blk, off) + s;
+    const T *src = segment_channels::member<T>(rec, off);
+    for (size_t i = 0; i < count; i++) dst[i * (size_t) B_] = src[i];
+  }
+  template <class C>
+  static std::function<bool(const pronto_wire::LogEvent &, Rec &, Stream &)> record_decoder(std::shared_ptr<C> ch, size_t bytes)
+  {
+    return [ch, bytes](const pronto_wire::LogEvent &ev, Rec &r, Stream &st) {
+      r.bytes.resize(bytes);
+      return ch->decode(ev.data.data(), ev.data.size(), st, r.bytes.data(), r.utime);
+    };
+  }
+  template <class T>
+  T *rows(uint8_t *blk, size_t off) const { return segment_channels::member<T>(blk, off, (size_t) B_); }   // a member's [count][B] rows in a block
+  uint8_t *block(size_t rec_bytes)   // a zeroed page-locked [rec_bytes][B] block
+  {
+    uint8_t *p = pinned<uint8_t>(rec_bytes * (size_t) B_);
+    std::fill_n(p, rec_bytes * (size_t) B_, (uint8_t) 0);
+    return p;
   }
   template <class T>
   T *pinned(size_t n)
@@ -726,9 +606,7 @@ private:
   MavStateEstimator *est_;
   int B_;
   int64_t base_ = INT64_MIN;
-  std::vector<double> final_vec_, final_quat_, final_cov_, final_ll_;
-  std::vector<int64_t> final_utime_;
-  std::vector<uint8_t> finished_;
+  segment_channels::Results results_;
   std::vector<uint8_t> got_ = std::vector<uint8_t>((size_t) B_, 0);
   std::vector<std::unique_ptr<Seg>> segs_;
   std::map<std::string, Chan> chans_;

@@ -22,11 +22,6 @@
 // idles (valid = 0) and its RESULT is its filter's head at the end of ITS log (finalState()).  What is counted instead of assumed:
 // order_violations, max_skew_us, ragged columns, undecodable events, read-ahead that hit its bound.
 //
-// New here: the reference's own IMU channel for Atlas logs -- bot_core::kvh_raw_imu_batch_t on ATLAS_IMU_BATCH
-// (motion_estimate/src/fusion/fusion.cpp:161-163 -> InsHandler::processMessageAtlas, sensor_handlers.cpp:165-252): one IMUStream
-// de-duplication state per SEGMENT (imu_stream.cpp:62-98) where the message is decoded, the notch cascade and the per-filter time
-// steps on the device (subscribeKvhBatch -> InsHandler::processMessageAtlasSegments).
-//
 // Host side only.  Header-only, POSIX (mmap).
 #pragma once
 
@@ -41,7 +36,7 @@
 #include <mutex>
 #include <thread>
 
-#include "mav_state_est_batch.hpp"
+#include "segment_channels.hpp"
 
 namespace MavStateEst {
 
@@ -153,10 +148,7 @@ public:
   int group = 16;                      // segments a host thread decodes together (16 floats = one cache line of a row)
   size_t readahead_cap = 4096;         // events a segment may read past its quota looking for a channel that has stopped
 
-  explicit SegmentStreamer(MavStateEstimator *est)
-      : est_(est), B_(est->B), final_vec_((size_t) est->n * est->B, 0.0), final_quat_((size_t) 4 * est->B, 0.0),
-        final_cov_((size_t) est->n * est->n * est->B, 0.0), final_ll_((size_t) est->B, 0.0), final_utime_((size_t) est->B, 0),
-        finished_((size_t) est->B, 0) {}
+  explicit SegmentStreamer(MavStateEstimator *est) : est_(est), B_(est->B), results_(est->n, est->B) {}
   ~SegmentStreamer()
   {
     est_->flushPending();   // (an update the estimator is holding back may still read the device chunks)
@@ -188,160 +180,66 @@ public:
   int segments() const { return (int) segs_.size(); }
 
   // ---- typed subscriptions: channel -> what FrontEnd::addSensor returned (or a handler method) ----
+  // What a channel reads of its wire type, its record and the message built from a block of records are segment_channels.hpp's; a slot
+  // without a message of a segment repeats the segment's last record on the channel (`carry`; else zeros), marked by the record's blank().
   // bot_core::ins_t (utime, gyro[3], accel[3]) -> InsHandler::processMessage with DEVICE arrays (frame rotation on the device)
   void subscribeIns(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                     std::function<void(const msgs::ins_t *)> cb)
   {
+    typedef segment_channels::InsChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentStreamer");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "gyro", "accel" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentStreamer: %s has no utime / gyro / accel members\n", type.c_str());
-    // record: f64 gyro[3] accel[3] | u8 valid
-    c.planes = { { 8, 6 }, { 1, 1 } };
-    c.decode = [plan](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->layout(ev.data, ev.dlen, st.shape, x, nullptr)) return false;
-      double v[6];
-      if (pronto_wire::Schema::Plan::gather_i64(st.shape, ev.data, 0, &utime, 1) != 1 || pronto_wire::Schema::Plan::gather_f64(st.shape, ev.data, 1, v, 3) != 3 ||
-          pronto_wire::Schema::Plan::gather_f64(st.shape, ev.data, 2, v + 3, 3) != 3)
-        return false;
-      memcpy(rec, v, sizeof v);
-      rec[48] = 1;
-      return true;
-    };
-    c.blank = [](uint8_t *rec) { rec[48] = 0; };   // (a filter without a message idles on its own last sample)
-    c.dispatch = [this, cb](const SlotView &v) {
-      msgs::ins_t m{ v.utime, BatchArray((const double *) v.dev(0), PB_DEVICE), BatchArray((const double *) v.dev(24), PB_DEVICE) };
-      m.valid = (const uint8_t *) v.dev(48);
+    c.planes = C::planes();
+    c.decode = [ch](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) { return ch->decode(ev.data, ev.dlen, st, rec, utime); };
+    c.blank = C::blank;
+    c.dispatch = [cb](const SlotView &v) {
+      const msgs::ins_t m = C::message(v.utime, v.dev_base, v.B, PB_DEVICE);
       cb(&m);
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::kvh_raw_imu_batch_t (utime, raw_imu[]{utime, packet_count, delta_rotation[3], linear_acceleration[3]}; raw_imu[0] is the
-  // NEWEST packet) -> InsHandler::processMessageAtlasSegments.  One IMUStream state per segment; atlas_filter = the handler's
-  // (true: de-duplicate, every new packet goes to the device notch cascade; false: newest packet, raw_dt from the two newest).
-  // max_packets: the most packets a message can carry (rows of the new-packet block).
+  // bot_core::kvh_raw_imu_batch_t -> InsHandler::processMessageAtlasSegments.  atlas_filter = the handler's; max_packets: rows of the
+  // new-packet block (a message with more NEW packets is counted into undecodable, its surplus packets are left out).
   void subscribeKvhBatch(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type, bool atlas_filter, int max_packets,
                          std::function<void(const msgs::kvh_raw_imu_segments_t *)> cb)
   {
+    auto ch = std::make_shared<segment_channels::KvhChannel>(schema, type, atlas_filter, max_packets, "SegmentStreamer");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(
-        schema->compile(type, { "utime", "raw_imu.utime", "raw_imu.packet_count", "raw_imu.delta_rotation", "raw_imu.linear_acceleration" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentStreamer: %s is not a kvh_raw_imu_batch_t\n", type.c_str());
-    const int MP = max_packets < 1 ? 1 : max_packets;
-    // record: f64 new_accel[MP][3] | f64 delta_rotation[3] | f64 raw_dt | i64 utime | i32 n_new | u8 valid
-    const size_t o_dr = (size_t) 24 * MP, o_rd = o_dr + 24, o_ut = o_rd + 8, o_nn = o_ut + 8, o_va = o_nn + 4;
-    c.planes = { { 8, 3 * MP + 5 }, { 4, 1 }, { 1, 1 } };
-    c.decode = [plan, MP, atlas_filter, o_dr, o_rd, o_ut, o_nn, o_va](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      static thread_local std::vector<int64_t> put, pcnt;
-      static thread_local std::vector<double> dr, la;
-      if (!plan->layout(ev.data, ev.dlen, st.shape, x, nullptr)) return false;
-      using P = pronto_wire::Schema::Plan;
-      if (P::gather_i64(st.shape, ev.data, 0, &utime, 1) != 1) return false;
-      size_t np = 0;
-      for (const auto &o : st.shape.ops)
-        if (o.slot == 1) np += o.count;
-      if (np < 1) return false;
-      put.resize(np); pcnt.resize(np); dr.resize(3 * np); la.resize(3 * np);
-      if (P::gather_i64(st.shape, ev.data, 1, put.data(), np) != np || P::gather_i64(st.shape, ev.data, 2, pcnt.data(), np) != np ||
-          P::gather_f64(st.shape, ev.data, 3, dr.data(), 3 * np) != 3 * np || P::gather_f64(st.shape, ev.data, 4, la.data(), 3 * np) != 3 * np)
-        return false;
-      double *acc = (double *) rec, *drot = (double *) (rec + o_dr), *raw_dt = (double *) (rec + o_rd);
-      int32_t n_new = 0;
-      if (!atlas_filter) {   // sensor_handlers.cpp:199-204: newest packet, raw_dt from the two newest
-        if (np < 2) return false;
-        for (int i = 0; i < 3; i++) { acc[i] = la[(size_t) i]; drot[i] = dr[(size_t) i]; }
-        *raw_dt = (double) (put[0] - put[1]) * 1E-6;
-        n_new = 1;
-      } else {               // IMUStream::convertFromLCMBatch (imu_stream.cpp:62-98), this segment's own state
-        if (pcnt[0] < st.last_packet) {   // "Detected time skip, resetting IMUStream" (:63-68)
-          st.last_packet = -1;
-          st.last_packet_utime = 0;
-        }
-        for (size_t i = np; i-- > 0;) {   // oldest first
-          if (pcnt[i] <= st.last_packet) continue;
-          const int64_t utime_delta = put[i] - st.last_packet_utime;
-          if (n_new < MP)
-            for (int a = 0; a < 3; a++) acc[(size_t) 3 * n_new + a] = la[3 * i + a];
-          n_new++;
-          for (int a = 0; a < 3; a++) drot[a] = dr[3 * i + a];   // (of the newest new packet in the end)
-          *raw_dt = (double) utime_delta * 1E-6;
-          st.last_packet = pcnt[i];
-          st.last_packet_utime = put[i];
-        }
-        if (n_new > MP) { st.overflow++; n_new = MP; }   // (more new packets than rows: the oldest ones were filtered... not at all -- counted)
-      }
-      memcpy(rec + o_ut, &utime, 8);
-      memcpy(rec + o_nn, &n_new, 4);
-      rec[o_va] = n_new > 0;
-      return true;
-    };
-    c.blank = [o_nn, o_va](uint8_t *rec) { const int32_t z = 0; memcpy(rec + o_nn, &z, 4); rec[o_va] = 0; };
-    c.dispatch = [this, cb, MP, o_dr, o_rd, o_ut, o_nn, o_va](const SlotView &v) {
-      msgs::kvh_raw_imu_segments_t m;
-      m.utime = v.utime;
-      m.max_new = MP;
-      m.new_accel = (const double *) v.dev(0);
-      m.delta_rotation = (const double *) v.dev(o_dr);
-      m.raw_dt = (const double *) v.dev(o_rd);
-      m.utimes = (const int64_t *) v.dev(o_ut);
-      m.n_new = (const int32_t *) v.dev(o_nn);
-      m.valid = (const uint8_t *) v.dev(o_va);
-      m.mem = PB_DEVICE;
+    c.planes = ch->planes();
+    c.decode = [ch](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) { return ch->decode(ev.data, ev.dlen, st, rec, utime); };
+    c.blank = [ch](uint8_t *rec) { ch->blank(rec); };
+    c.dispatch = [cb, ch](const SlotView &v) {
+      const msgs::kvh_raw_imu_segments_t m = ch->message(v.utime, v.dev_base, v.B, PB_DEVICE);
       cb(&m);
     };
     chans_[channel] = std::move(c);
   }
-  // bot_core::joint_state_t -> LegOdoHandler::processMessage with DEVICE blocks and per-filter message times read in place
+  // bot_core::joint_state_t -> LegOdoHandler::processMessage with DEVICE blocks and per-filter message times read in place.  The first
+  // message of the first lead configures the channel: its joint list sizes the record, and a message with another list is rejected.
   void subscribeJointState(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                            std::function<void(const msgs::joint_state_t *)> cb)
   {
-    Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(
-        schema->compile(type, { "utime", "joint_name", "joint_position", "joint_velocity", "joint_effort" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentStreamer: %s is not a joint_state_t\n", type.c_str());
+    typedef segment_channels::JointStateChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentStreamer");
     auto js = std::make_shared<JointInfo>();
-    // record (after configure): i64 utime | f32 position[n] velocity[n] effort[n] | u8 valid
-    c.configure = [plan, js](const MappedLog::Event &ev, Chan &self) {
-      std::vector<pronto_wire::Schema::Extracted> x;
-      pronto_wire::Schema::Plan::Shape sh;
-      if (!plan->run(ev.data, ev.dlen, x, sh, nullptr) || x[1].str.empty()) return false;
-      js->names = x[1].str;
-      js->n = js->names.size();
-      js->hash = names_hash(js->names);
-      self.planes = { { 8, 1 }, { 4, (int) (3 * js->n) }, { 1, 1 } };
+    Chan c;
+    c.configure = [ch, js](const MappedLog::Event &ev, Chan &self) {
+      SegChan st;
+      const std::vector<std::string> *names = nullptr;
+      if (!ch->open(ev.data, ev.dlen, st, &names) || names->empty()) return false;
+      js->names = *names;
+      js->hash = st.names_hash;
+      js->lay = C::Layout(names->size());
+      self.planes = js->lay.planes();
       return true;
     };
-    c.decode = [plan, js](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      bool rebuilt = false;
-      if (!plan->layout(ev.data, ev.dlen, st.shape, x, &rebuilt)) return false;
-      if (rebuilt) st.names_hash = names_hash(x[1].str);   // a new joint list (normally: the first message of the segment)
+    c.decode = [ch, js](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
       // one robot model for the batch: the same joints in the same order as the lead's
-      if (st.names_hash != js->hash) return false;
-      using P = pronto_wire::Schema::Plan;
-      const size_t n = js->n;
-      float *f = (float *) (rec + 8);
-      if (P::gather_i64(st.shape, ev.data, 0, &utime, 1) != 1 || P::gather_f32(st.shape, ev.data, 2, f, n) != n ||
-          P::gather_f32(st.shape, ev.data, 3, f + n, n) != n || P::gather_f32(st.shape, ev.data, 4, f + 2 * n, n) != n)
-        return false;
-      memcpy(rec, &utime, 8);
-      rec[8 + 12 * n] = 1;
-      return true;
+      return ch->open(ev.data, ev.dlen, st) && st.names_hash == js->hash && ch->read(ev.data, st, js->lay, rec, utime);
     };
-    c.blank = [js](uint8_t *rec) { rec[8 + 12 * js->n] = 0; };   // (the block keeps this filter's last message; it is masked)
-    c.dispatch = [this, cb, js](const SlotView &v) {
-      msgs::joint_state_t m;
-      m.utime = v.utime;
-      m.joint_name = js->names;
-      const size_t n = js->n;
-      m.joint_position = (const float *) v.dev(8);
-      m.joint_velocity = (const float *) v.dev(8 + 4 * n);
-      m.joint_effort = (const float *) v.dev(8 + 8 * n);
-      m.mem = PB_DEVICE;
-      m.utimes = (const int64_t *) v.dev(0);
-      m.valid = (const uint8_t *) v.dev(8 + 12 * n);
-      m.times_mem = PB_DEVICE;
+    c.blank = [js](uint8_t *rec) { C::blank(js->lay, rec); };
+    c.dispatch = [cb, js](const SlotView &v) {
+      const msgs::joint_state_t m = C::message(v.utime, js->names, js->lay, v.B, (const float *) v.dev(js->lay.POSITION), PB_DEVICE, v.dev_base, PB_DEVICE);
       cb(&m);
     };
     chans_[channel] = std::move(c);
@@ -351,17 +249,14 @@ public:
   void subscribeForceTorque(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                             std::function<void(const float *abs_force_z_dev)> cb)
   {
+    auto ch = std::make_shared<segment_channels::ForceTorqueChannel>(schema, type, "SegmentStreamer");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "sensors.force" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentStreamer: %s is not a six_axis_force_torque_array_t\n", type.c_str());
-    c.planes = { { 4, 2 } };
-    c.decode = [plan](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->layout(ev.data, ev.dlen, st.shape, x, nullptr)) return false;
-      double f[6];
-      if (pronto_wire::Schema::Plan::gather_i64(st.shape, ev.data, 0, &utime, 1) != 1 || pronto_wire::Schema::Plan::gather_f64(st.shape, ev.data, 1, f, 6) != 6) return false;
-      const float a[2] = { (float) fabs(f[2]), (float) fabs(f[5]) };   // FootSensing(fabs(...)), float members
-      memcpy(rec, a, 8);
+    c.planes = { { 4, 2 } };   // record: f32 |force z| left, right
+    c.decode = [ch](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
+      double fz[2];
+      if (!ch->decode(ev.data, ev.dlen, st, fz, utime)) return false;
+      const float a[2] = { (float) fabs(fz[0]), (float) fabs(fz[1]) };   // FootSensing(fabs(...)), float members
+      memcpy(rec, a, sizeof a);
       return true;
     };
     c.blank = [](uint8_t *) {};   // (the handler keeps the LAST force/torque message, per filter: a missing one changes nothing)
@@ -373,32 +268,15 @@ public:
   void subscribePose(const std::string &channel, const pronto_wire::Schema *schema, const std::string &type,
                      std::function<void(const msgs::pose_t *)> cb)
   {
+    typedef segment_channels::PoseChannel C;
+    auto ch = std::make_shared<C>(schema, type, "SegmentStreamer");
     Chan c;
-    auto plan = std::make_shared<pronto_wire::Schema::Plan>(schema->compile(type, { "utime", "pos", "vel", "orientation" }));
-    if (!plan->ok()) fprintf(stderr, "SegmentStreamer: %s is not a pose_t\n", type.c_str());
-    c.planes = { { 8, 10 }, { 1, 1 } };
+    c.planes = C::planes();
     c.carry = false;
-    c.decode = [plan](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) {
-      static thread_local std::vector<pronto_wire::Schema::Extracted> x;
-      if (!plan->layout(ev.data, ev.dlen, st.shape, x, nullptr)) return false;
-      using P = pronto_wire::Schema::Plan;
-      double v[10];
-      if (P::gather_i64(st.shape, ev.data, 0, &utime, 1) != 1 || P::gather_f64(st.shape, ev.data, 1, v, 3) != 3 || P::gather_f64(st.shape, ev.data, 2, v + 3, 3) != 3 ||
-          P::gather_f64(st.shape, ev.data, 3, v + 6, 4) != 4)
-        return false;
-      memcpy(rec, v, sizeof v);
-      rec[80] = 1;
-      return true;
-    };
-    c.blank = [](uint8_t *rec) {
-      const double none[10] = { 0, 0, 0, 0, 0, 0, 1, 0, 0, 0 };
-      memcpy(rec, none, sizeof none);
-      rec[80] = 0;
-    };
+    c.decode = [ch](const MappedLog::Event &ev, SegChan &st, uint8_t *rec, int64_t &utime) { return ch->decode(ev.data, ev.dlen, st, rec, utime); };
+    c.blank = C::blank;
     c.dispatch = [cb](const SlotView &v) {
-      msgs::pose_t m{ v.utime, BatchArray((const double *) v.host(0), PB_HOST), BatchArray((const double *) v.host(24), PB_HOST),
-                      BatchArray((const double *) v.host(48), PB_HOST) };
-      m.valid = (const uint8_t *) v.host(80);
+      const msgs::pose_t m = C::message(v.utime, v.host_base, v.B);
       cb(&m);
     };
     chans_[channel] = std::move(c);
@@ -406,30 +284,19 @@ public:
   // pronto::update_t (pronto_wire.hpp) -> FovisHandler::processMessage.  timestamp / prev_timestamp are the lead's.  Sparse: PB_HOST.
   void subscribeUpdate(const std::string &channel, std::function<void(const msgs::update_t *)> cb)
   {
+    typedef segment_channels::UpdateChannel C;
     Chan c;
-    c.planes = { { 8, 7 }, { 1, 1 } };
+    c.planes = C::planes();
     c.carry = false;
-    c.decode = [](const MappedLog::Event &ev, SegChan &, uint8_t *rec, int64_t &utime) {
-      pronto_wire::update_t w;
-      if (w.decode(ev.data, ev.dlen) < 0) return false;
-      utime = w.timestamp;
-      memcpy(rec, w.translation, 24);
-      memcpy(rec + 24, w.rotation, 32);
-      rec[56] = w.estimate_status == pronto_wire::update_t::ESTIMATE_VALID;
-      return true;
-    };
+    c.decode = [](const MappedLog::Event &ev, SegChan &, uint8_t *rec, int64_t &utime) { return C::decode(ev.data, ev.dlen, rec, utime, nullptr); };
     c.aux = [](const MappedLog::Event &ev) {   // the lead's prev_timestamp behind its timestamp
-      pronto_wire::update_t w;
-      return w.decode(ev.data, ev.dlen) < 0 ? (int64_t) 0 : w.prev_timestamp - w.timestamp;
+      uint8_t rec[C::BYTES];
+      int64_t utime, prev_behind = 0;
+      return C::decode(ev.data, ev.dlen, rec, utime, &prev_behind) ? prev_behind : (int64_t) 0;
     };
-    c.blank = [](uint8_t *rec) {
-      const double none[7] = { 0, 0, 0, 1, 0, 0, 0 };
-      memcpy(rec, none, sizeof none);
-      rec[56] = 0;
-    };
+    c.blank = C::blank;
     c.dispatch = [cb](const SlotView &v) {
-      msgs::update_t m{ v.utime, v.utime + v.aux, (const uint8_t *) v.host(56), BatchArray((const double *) v.host(0), PB_HOST),
-                        BatchArray((const double *) v.host(24), PB_HOST) };
+      const msgs::update_t m = C::message(v.utime, v.aux, v.host_base, v.B);
       cb(&m);
     };
     chans_[channel] = std::move(c);
@@ -525,31 +392,21 @@ public:
       stats.segment_messages += sg->messages;
       stats.ragged += sg->ragged;
       stats.readahead_capped += sg->capped;
-      for (const SegChan &sc : sg->chan) stats.undecodable += sc.overflow;
+      for (const SegChan &sc : sg->chan) stats.undecodable += sc.overflow;   // (KVH: more new packets than rows)
       sg->undecodable = sg->order_violations = sg->max_skew = sg->messages = sg->ragged = sg->capped = 0;
     }
     return stats.batches;
   }
 
   // the head of every segment's filter at the end of ITS log (valid after run(); columns of segments never added are zero)
-  void finalState(RBIS &state, RBIM &cov) const
-  {
-    state = RBIS(est_->n, B_);
-    cov = RBIM(est_->n, B_);
-    state.vec = final_vec_;
-    state.quat = final_quat_;
-    cov.m = final_cov_;
-  }
-  const std::vector<double> &finalLogLikelihood() const { return final_ll_; }
-  int64_t finalUtime(int s) const { return final_utime_[(size_t) s]; }
+  void finalState(RBIS &state, RBIM &cov) const { results_.finalState(state, cov); }
+  const std::vector<double> &finalLogLikelihood() const { return results_.finalLogLikelihood(); }
+  int64_t finalUtime(int s) const { return results_.finalUtime(s); }
 
 private:
-  struct Plane { int elem, count; };
-  struct SegChan {   // what one segment remembers about one channel
-    pronto_wire::Schema::Plan::Shape shape;
-    uint64_t names_hash = 0;
-    std::vector<uint8_t> last;        // its last record on this channel (what a slot without a message repeats)
-    int64_t last_packet = -1, last_packet_utime = 0, overflow = 0;   // IMUStream (imu_stream.hpp:10-37)
+  typedef segment_channels::Plane Plane;
+  struct SegChan : segment_channels::ChannelState {   // what one segment remembers about one channel ...
+    std::vector<uint8_t> last;   // ... and its last record on the channel (what a slot without a message repeats)
   };
   struct SlotView {
     uint8_t *host_base, *dev_base;
@@ -571,10 +428,10 @@ private:
     std::string name;
     std::vector<std::pair<uint32_t, uint8_t>> elems;   // (record offset, element size) of every element, for the transposition
   };
-  struct JointInfo {
+  struct JointInfo {   // the joint list that configured the channel (of the first lead's first message) and the record it sizes
     std::vector<std::string> names;
-    size_t n = 0;
     uint64_t hash = 0;
+    segment_channels::JointStateChannel::Layout lay{ 0 };
   };
   struct Seg {
     std::shared_ptr<MappedLog> log;
@@ -600,15 +457,6 @@ private:
     uint8_t *host = nullptr, *dev = nullptr;
   };
 
-  static uint64_t names_hash(const std::vector<std::string> &names)
-  {
-    uint64_t h = 1469598103934665603ull;   // FNV-1a over the names and their boundaries
-    for (const std::string &nm : names) {
-      for (unsigned char ch : nm) h = (h ^ ch) * 1099511628211ull;
-      h = (h ^ 0xffu) * 1099511628211ull;
-    }
-    return h;
-  }
   int channel_of(const MappedLog::Event &ev) const
   {
     for (const Chan *c : chan_list_)
@@ -710,7 +558,7 @@ private:
         std::sort(rest.begin(), rest.end());   // (file order: the event that did not fit may itself have come from the list)
         lead.carry.swap(rest);
       }
-      peek_end(lead, last_k, *ck, first_alive_);
+      peek_end(lead, last_k, ck->ends, first_alive_);
       if (ck->slots.empty()) {   // the lead had nothing decodable left: the next segment leads; its end is finalized in front of the next chunk
         for (const auto &e : ck->ends) pending_ends.push_back({ -1, e.second });
         continue;
@@ -817,7 +665,7 @@ private:
               std::sort(keep.begin(), keep.end());
               sg.carry.swap(keep);
             }
-            peek_end_into(sg, last, ends_of[(size_t) g], s);
+            peek_end(sg, last, ends_of[(size_t) g], s);
           }
           // slots without a message of this segment: its last record on that channel, marked "no message"
           for (int k = 0; k < n_slots; k++) {
@@ -880,27 +728,18 @@ private:
   }
   // Does the segment have a subscribed event left?  Reads ahead to the next one (kept for the next chunk) like SegmentBatcher's
   // fill(); at the end of the log the run is complete: it is finalized right behind the last slot it had a message in.
-  void peek_end_into(Seg &sg, int last_slot, std::vector<std::pair<int, int>> &ends, int s)
+  void peek_end(Seg &sg, int last_slot, std::vector<std::pair<int, int>> &ends, int s)
   {
     if (sg.ended || !sg.carry.empty()) return;
     MappedLog::Event ev;
-    while (next_event_from_log(sg, ev)) {
+    size_t carry_at = 0;   // (nothing carried: next_event reads the log)
+    while (next_event(sg, carry_at, ev)) {
       if (channel_of(ev) < 0) continue;
       sg.carry.push_back(ev.at);
       return;
     }
     sg.ended = true;
     ends.push_back({ last_slot, s });
-  }
-  void peek_end(Seg &sg, int last_slot, Chunk &ck, int s) { peek_end_into(sg, last_slot, ck.ends, s); }
-  bool next_event_from_log(Seg &sg, MappedLog::Event &ev)
-  {
-    while (!sg.eof) {
-      if (!sg.log->next(sg.pos, ev) || (sg.end_timestamp > 0 && ev.timestamp >= sg.end_timestamp)) { sg.eof = true; return false; }
-      if (ev.timestamp < sg.start_timestamp) continue;
-      return true;
-    }
-    return false;
   }
 
   // the runs that ended right behind slot k of this chunk: read their heads (applies whatever the estimator holds back first)
@@ -914,36 +753,14 @@ private:
       int first = it->second, count = 1;
       ++it;
       while (it != ck.ends.end() && it->first == k && it->second == first + count) { count++; ++it; }
-      finalize(first, count);
+      results_.finalize(est_, first, count, "SegmentStreamer");
     }
     stats.t_final += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
-  void finalize(int first, int count)
-  {
-    const int n = est_->n;
-    est_->flushPending();
-    std::vector<double> v((size_t) n * count), q((size_t) 4 * count), c((size_t) n * n * count), l((size_t) count);
-    if (pb_get_head(est_->ctx, first, count, v.data(), q.data(), c.data(), l.data(), PB_HOST) != PB_OK) {
-      fprintf(stderr, "SegmentStreamer: %s\n", pb_last_error(est_->ctx));
-      return;
-    }
-    for (int k = 0; k < count; k++) {
-      const size_t s = (size_t) (first + k);
-      for (int i = 0; i < n; i++) final_vec_[(size_t) i * B_ + s] = v[(size_t) i * count + k];
-      for (int i = 0; i < 4; i++) final_quat_[(size_t) i * B_ + s] = q[(size_t) i * count + k];
-      for (int i = 0; i < n * n; i++) final_cov_[(size_t) i * B_ + s] = c[(size_t) i * count + k];
-      final_ll_[s] = l[(size_t) k];
-      final_utime_[s] = est_->head_utime;
-      finished_[s] = 1;
-    }
-  }
-
   MavStateEstimator *est_;
   int B_;
   int64_t base_ = INT64_MIN;
-  std::vector<double> final_vec_, final_quat_, final_cov_, final_ll_;
-  std::vector<int64_t> final_utime_;
-  std::vector<uint8_t> finished_;
+  segment_channels::Results results_;
   std::vector<std::unique_ptr<Seg>> segs_;
   std::map<std::string, Chan> chans_;
   std::vector<Chan *> chan_list_;

@@ -5,7 +5,8 @@
 //   * pronto_wire::LogReader::next, MappedLog::next / seek                     (pronto_wire.hpp, segment_stream.hpp)
 //   * pronto_wire::Schema::parse / decode, Schema::Plan::run and ::layout with a WARM Shape (lcm_schema.hpp)
 //   * pronto_wire::{filter_state_t, indexed_measurement_t, update_t}::decode   (pronto_wire.hpp)
-//   * SegmentBatcher::run and SegmentStreamer::run on damaged log files        (segment_batcher.hpp, segment_stream.hpp)
+//   * SegmentBatcher::run and SegmentStreamer::run on damaged log files        (segment_batcher.hpp, segment_stream.hpp, and the channel
+//     decoders both go through: segment_channels.hpp; what they hand over is checked by segment_messages.cpp)
 //   * ModelClient::fromURDFString / chainTo                                     (mav_state_est_batch.hpp)
 // The C ABI is replaced by HOST stubs generated from include/pronto_batch.h by the test (device blocks are plain heap blocks, so the
 // sanitizer also sees every byte the replayers write into their chunks and every size they pass to an upload): this program is test

@@ -21,6 +21,7 @@ def build_exe(oracle, name="test_shim"):
     src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
     deps = [src, os.path.join(ROOT, "tests", "cpp", "test_n.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est_batch.hpp"),
             os.path.join(ROOT, "pronto_amd", "csrc", "mav_state_est.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "segment_batcher.hpp"), os.path.join(ROOT, "pronto_amd", "csrc", "segment_stream.hpp"),
+            os.path.join(ROOT, "pronto_amd", "csrc", "segment_channels.hpp"),
             os.path.join(ROOT, "pronto_amd", "csrc", "lcm_schema.hpp"),
             os.path.join(ROOT, "pronto_amd", "csrc", "pronto_wire.hpp"),
             os.path.join(ROOT, "include", "pronto_batch.h"), _lib.LIB_PATH]
