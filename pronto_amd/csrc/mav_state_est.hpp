@@ -181,6 +181,36 @@ struct BatchArray {
   BatchArray() {}
   BatchArray(const double *ptr, int m) : p(ptr), mem(m) {}
 };
+// What the handlers share when they take a host message over (the update objects own their host payloads, see below):
+// the values per row -- one per filter, or one for all (PB_HOST_BROADCAST) --
+inline size_t batch_per(int mem, int B) { return mem == PB_HOST_BROADCAST ? 1 : (size_t) B; }
+// an owned copy of `rows` host rows of a message array,
+inline std::vector<double> own_rows(const BatchArray &a, size_t rows, int B) { return std::vector<double>(a.p, a.p + rows * batch_per(a.mem, B)); }
+// and of a host mask [B]: none without a mask, and none for one robot's message (it is for every filter)
+inline std::vector<uint8_t> own_mask(const uint8_t *mask, int mem, int B)
+{
+  return (mask != nullptr && mem == PB_HOST) ? std::vector<uint8_t>(mask, mask + B) : std::vector<uint8_t>();
+}
+// Hamilton product r = a * b (w,x,y,z); r must not be a or b
+inline void quat_mult(const double a[4], const double b[4], double r[4])
+{
+  r[0] = a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3];
+  r[1] = a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2];
+  r[2] = a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1];
+  r[3] = a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0];
+}
+// A handler's report of a failed library call: "<who>: <pb_last_error>" on stderr.  Yields nullptr, so that a handler that gives the
+// message up writes `return pb_report(...)`; the sibling ends the program like every bad configuration (libbot's *_or_fail behaviour).
+inline std::nullptr_t pb_report(const char *who, pb_ctx *ctx)
+{
+  fprintf(stderr, "%s: %s\n", who, pb_last_error(ctx));
+  return nullptr;
+}
+[[noreturn]] inline void pb_report_exit(const char *who, pb_ctx *ctx)
+{
+  pb_report(who, ctx);
+  exit(1);
+}
 
 class MavStateEstimator;
 
@@ -223,6 +253,14 @@ struct DeviceBlock {
   DeviceBlock(const DeviceBlock &) = delete;
   DeviceBlock &operator=(const DeviceBlock &) = delete;
 };
+// a block of `pool` as an update owns it (back into the pool with its last owner), or null: pb_malloc failed.  fresh: never used before
+inline std::shared_ptr<DeviceBlock> take_block(const std::shared_ptr<DevicePool> &pool, bool *fresh = nullptr)
+{
+  bool is_fresh = false;
+  void *p = pool->get(is_fresh);
+  if (fresh != nullptr) *fresh = is_fresh;
+  return p != nullptr ? std::make_shared<DeviceBlock>(pool, p) : nullptr;
+}
 
 // ---------------------------------------------------------------------------------------------------------------
 // update objects (rbis_update_interface.hpp)
@@ -392,6 +430,25 @@ public:
                                     orientation.p, mask, measurement.mem);
   }
 };
+// The two measurements built from a HOST message in `mem` -- PB_HOST, or PB_HOST_BROADCAST: one robot's z [m] (and quat [4]) for every
+// filter.  The update owns z, R (per r_kind; a per-filter R lives where z does), the mask and the quaternion.
+inline RBISIndexedMeasurement *hostIndexedMeasurement(const std::vector<int> &index, std::vector<double> z, std::vector<double> R, int r_kind,
+                                                      std::vector<uint8_t> mask, int mem, RBISUpdateInterface::sensor_enum sensor, int64_t utime)
+{
+  auto *u = new RBISIndexedMeasurement(index, std::move(z), std::move(R), r_kind, std::move(mask), sensor, utime);
+  u->measurement.mem = mem;
+  if (r_kind != PB_R_DIAG_BROADCAST) u->cov_mem = mem;
+  return u;
+}
+// (every handler that measures an orientation has one diagonal R for all filters: PB_R_DIAG_BROADCAST)
+inline RBISIndexedPlusOrientationMeasurement *hostIndexedPlusOrientationMeasurement(const std::vector<int> &index, std::vector<double> z, std::vector<double> R_diag,
+                                                                                    std::vector<double> quat, std::vector<uint8_t> mask, int mem,
+                                                                                    RBISUpdateInterface::sensor_enum sensor, int64_t utime)
+{
+  auto *u = new RBISIndexedPlusOrientationMeasurement(index, std::move(z), std::move(R_diag), PB_R_DIAG_BROADCAST, std::move(quat), std::move(mask), sensor, utime);
+  u->measurement.mem = u->orientation.mem = mem;
+  return u;
+}
 
 // An update written against the REFERENCE's contract (rbis_update_interface.hpp:14-35):
 //     virtual void updateFilter(const RBIS & prior_state, const RBIM & prior_cov, double prior_loglikelihood) = 0;

@@ -378,22 +378,13 @@ public:
                              p.utime_delta * 1E-6 };
       return processMessageAtlasPacket(&m, est);
     }
-    if (!notch_initialised) {
-      if (pb_imu_notch_init(est->ctx, notch_freq, 1000) != PB_OK) {  // fs = 1000 (:32)
-        fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-        exit(1);
-      }
-      notch_initialised = true;
-    }
+    initNotch(est);
     IMUBatch batch = imu_data_.convertFromLCMBatch(msg);
     if (batch.packets.empty()) return nullptr;  // :181-187 "happens all the time at 1kHz"
     const size_t np = batch.packets.size();
     std::vector<double> acc((size_t) np * 3 * B), filt((size_t) 3 * B);
     for (size_t p = 0; p < np; p++) memcpy(&acc[p * 3 * B], batch.packets[p].linear_acceleration, sizeof(double) * 3 * B);
-    if (pb_imu_notch(est->ctx, (int) np, acc.data(), filt.data(), PB_HOST) != PB_OK) {
-      fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-      return nullptr;
-    }
+    if (pb_imu_notch(est->ctx, (int) np, acc.data(), filt.data(), PB_HOST) != PB_OK) return pb_report("InsHandler", est->ctx);
     const IMUPacket &p = batch.packets.back();  // the most recent filtered packet (:191-196)
     msgs::kvh_raw_imu_t m{ msg->utime, BatchArray(p.delta_rotation, PB_HOST), BatchArray(filt.data(), PB_HOST),
                            p.utime_delta * 1E-6 };
@@ -402,6 +393,13 @@ public:
 
   double notch_freq = 0.0;
   bool notch_initialised = false;
+  // the device-side cascade (one state per filter), once
+  void initNotch(MavStateEstimator *est)
+  {
+    if (notch_initialised) return;
+    if (pb_imu_notch_init(est->ctx, notch_freq, 1000) != PB_OK) pb_report_exit("InsHandler", est->ctx);  // fs = 1000 (:32)
+    notch_initialised = true;
+  }
   IMUStream imu_data_;
   std::vector<IIRNotch> host_notch_;  // [axis][stage], broadcast messages only
 
@@ -423,36 +421,17 @@ public:
     const size_t B = (size_t) est->B;
     const double *accel = msg->new_accel;   // atlas_filter == false: row 0 is the newest packet, unfiltered (:199-204)
     if (atlas_filter) {
-      if (!notch_initialised) {
-        if (pb_imu_notch_init(est->ctx, notch_freq, 1000) != PB_OK) {  // fs = 1000 (:32)
-          fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-          exit(1);
-        }
-        notch_initialised = true;
-      }
+      initNotch(est);
       if (msg->n_new == nullptr) return nullptr;
-      if (msg->mem == PB_DEVICE) {
-        if (notch_out_dev_ == nullptr) {
-          void *d = nullptr;
-          if (pb_malloc(est->ctx, sizeof(double) * 3 * B, &d) != PB_OK) {
-            fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-            exit(1);
-          }
-          notch_out_dev_ = std::make_shared<DeviceBlock>(std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 3 * B), d);
-        }
-        accel = (const double *) notch_out_dev_->p;
-        if (pb_imu_notch_counts(est->ctx, msg->max_new, msg->n_new, msg->new_accel, (double *) notch_out_dev_->p, PB_DEVICE) != PB_OK) {
-          fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-          return nullptr;
-        }
-      } else {
-        notch_out_host_.resize(3 * B);
-        if (pb_imu_notch_counts(est->ctx, msg->max_new, msg->n_new, msg->new_accel, notch_out_host_.data(), PB_HOST) != PB_OK) {
-          fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-          return nullptr;
-        }
-        accel = notch_out_host_.data();
+      if (msg->mem == PB_DEVICE && notch_out_dev_ == nullptr) {
+        void *d = nullptr;
+        if (pb_malloc(est->ctx, sizeof(double) * 3 * B, &d) != PB_OK) pb_report_exit("InsHandler", est->ctx);
+        notch_out_dev_ = std::make_shared<DeviceBlock>(std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 3 * B), d);
       }
+      if (msg->mem == PB_HOST) notch_out_host_.resize(3 * B);
+      double *filtered = msg->mem == PB_DEVICE ? (double *) notch_out_dev_->p : notch_out_host_.data();
+      if (pb_imu_notch_counts(est->ctx, msg->max_new, msg->n_new, msg->new_accel, filtered, msg->mem) != PB_OK) return pb_report("InsHandler", est->ctx);
+      accel = filtered;
     }
     return buildOnDevice(est, msg->delta_rotation, accel, msg->raw_dt, msg->utimes, msg->utime, msg->valid, true, msg->mem);
   }
@@ -505,10 +484,9 @@ public:
       return false;
     }
     init_counter++;
-    const bool bcast = update->imu_block.mem == PB_HOST_BROADCAST;
-    const size_t per = bcast ? 1 : (size_t) B;
+    const size_t per = batch_per(update->imu_block.mem, B);
     for (int b = 0; b < B; b++) {
-      const size_t sb = bcast ? 0 : (size_t) b;
+      const size_t sb = (per == 1) ? 0 : (size_t) b;
       for (int i = 0; i < 3; i++) {
         gyro_bias_sum[(size_t) i * B + b] += update->owned[(size_t) i * per + sb];            // :291
         g_vec_sum[(size_t) i * B + b] += -update->owned[(size_t) (3 + i) * per + sb];         // :289
@@ -516,7 +494,7 @@ public:
     }
     delete update;
     if (msg->mag.p != nullptr && msg->mag.mem != PB_DEVICE) {  // :147-149, :290
-      const size_t mper = (msg->mag.mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
+      const size_t mper = batch_per(msg->mag.mem, B);
       for (int b = 0; b < B; b++) {
         const size_t sb = (mper == 1) ? 0 : (size_t) b;
         const double ms[3] = { msg->mag.p[sb], msg->mag.p[mper + sb], msg->mag.p[2 * mper + sb] };
@@ -545,10 +523,8 @@ public:
       double qg[4];
       quat_from_two_vectors(g_est, minus_z, qg);                                               // :314-315
       const double q0[4] = { init_state.q(0, b), init_state.q(1, b), init_state.q(2, b), init_state.q(3, b) };
-      const double qn[4] = { q0[0] * qg[0] - q0[1] * qg[1] - q0[2] * qg[2] - q0[3] * qg[3],
-                             q0[0] * qg[1] + q0[1] * qg[0] + q0[2] * qg[3] - q0[3] * qg[2],
-                             q0[0] * qg[2] - q0[1] * qg[3] + q0[2] * qg[0] + q0[3] * qg[1],
-                             q0[0] * qg[3] + q0[1] * qg[2] - q0[2] * qg[1] + q0[3] * qg[0] };
+      double qn[4];
+      quat_mult(q0, qg, qn);
       for (int i = 0; i < 4; i++) init_state.q(i, b) = qn[i];                                   // :320
       for (int r = 0; r < 2; r++)
         for (int c = 0; c < 2; c++)
@@ -564,10 +540,8 @@ public:
         double qm[4];
         quat_from_two_vectors(m_est, unit_y, qm);
         const double q1[4] = { init_state.q(0, b), init_state.q(1, b), init_state.q(2, b), init_state.q(3, b) };
-        const double qy[4] = { qm[0] * q1[0] - qm[1] * q1[1] - qm[2] * q1[2] - qm[3] * q1[3],
-                               qm[0] * q1[1] + qm[1] * q1[0] + qm[2] * q1[3] - qm[3] * q1[2],
-                               qm[0] * q1[2] - qm[1] * q1[3] + qm[2] * q1[0] + qm[3] * q1[1],
-                               qm[0] * q1[3] + qm[1] * q1[2] - qm[2] * q1[1] + qm[3] * q1[0] };
+        double qy[4];
+        quat_mult(qm, q1, qy);
         for (int i = 0; i < 4; i++) init_state.q(i, b) = qy[i];                                 // quat_mag * orientation
         init_cov(RBIS::chi_ind + 2, RBIS::chi_ind + 2, b) = default_cov(RBIS::chi_ind + 2, RBIS::chi_ind + 2, b);
       }
@@ -601,20 +575,17 @@ private:
                                      int64_t utime, const uint8_t *valid, bool atlas, int mem)
   {
     if (!ins_pool_) ins_pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 7 * (size_t) est->B + (size_t) est->B);
-    bool fresh = false;
-    void *blk = ins_pool_->get(fresh);
+    const std::shared_ptr<DeviceBlock> block = take_block(ins_pool_);   // (unused, it goes back to the pool when this call fails)
+    void *blk = block ? block->p : nullptr;
     // (the block is [7][B] doubles + a [B] mask behind it: the update OWNS its copy of the mask -- a host mask is gone when the handler
     // returns, and a device mask inside a replayer's chunk buffer may be overwritten before a held-back step has run)
     uint8_t *mask_out = (blk != nullptr && valid != nullptr) ? (uint8_t *) ((double *) blk + (size_t) 7 * est->B) : nullptr;
     if (blk == nullptr ||
         pb_ins_body_block(est->ctx, gyro, accel, raw_dt, utimes, utime, valid, ins_to_body.rot_quat, atlas ? ins_to_body.trans_vec : nullptr, dt,
-                          atlas ? 1 : 0, mem, (double *) blk, mask_out) != PB_OK) {
-      fprintf(stderr, "InsHandler: %s\n", pb_last_error(est->ctx));
-      if (blk) ins_pool_->free_.push_back(blk);
-      return nullptr;
-    }
+                          atlas ? 1 : 0, mem, (double *) blk, mask_out) != PB_OK)
+      return pb_report("InsHandler", est->ctx);
     auto *u = new RBISIMUProcessStep(BatchArray((const double *) blk, PB_DEVICE), cov_gyro, cov_accel, cov_gyro_bias, cov_accel_bias, utime);
-    u->owned_dev = std::make_shared<DeviceBlock>(ins_pool_, blk);
+    u->owned_dev = block;
     u->valid_dev = mask_out;
     u->may_idle = mask_out != nullptr && (mem != PB_HOST || std::find(valid, valid + est->B, (uint8_t) 0) != valid + est->B);
     return u;
@@ -947,6 +918,12 @@ public:
   }
   ~LegOdoHandler() { delete leg_odo_common_; }
   void forceTorqueHandler() { force_torque_init_ = true; }
+  // rbis_legodo_update.cpp:208-211: the gate in front of every entry point
+  bool forceTorqueSeen() const
+  {
+    if (!force_torque_init_) fprintf(stdout, "Force/Torque message not received yet, not integrating leg odometry =========================\n");
+    return force_torque_init_;
+  }
   // rbis_legodo_update.cpp:195-204: keep the last force/torque message; processMessage reads |force z| of the two feet
   void forceTorqueHandler(const msgs::six_axis_force_torque_array_t *msg, int B)
   {
@@ -1012,10 +989,7 @@ public:
     }
     // "ignore the calculated velocity at launch" is counted per filter on the device (valid ticks only, like :243-268)
     if (!bad) bad = pb_legodo_set_zero_initial_velocity(est->ctx, zero_initial_velocity) != PB_OK;
-    if (bad) {
-      fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-      exit(1);
-    }
+    if (bad) pb_report_exit("LegOdoHandler", est->ctx);
     // per update: the measurement block -- z and the diagonal of R, [6][B] (lin_rate) or [12][B] doubles -- and its mask(s) [2][B]
     pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 12 * (size_t) B + 2 * (size_t) B);
     legodo_ready_ = true;
@@ -1078,10 +1052,7 @@ public:
       if (sweep_rows_[row].empty()) std::fill(block.begin() + (size_t) row * B, block.begin() + (size_t) (row + 1) * B, cfg(row));
       else std::copy(sweep_rows_[row].begin(), sweep_rows_[row].end(), block.begin() + (size_t) row * B);
     }
-    if (pb_legodo_set_param_block(est->ctx, block.data(), PB_HOST) != PB_OK) {
-      fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-      exit(1);
-    }
+    if (pb_legodo_set_param_block(est->ctx, block.data(), PB_HOST) != PB_OK) pb_report_exit("LegOdoHandler", est->ctx);
     sweep_dirty_ = false;
   }
   // fksolver_->JntToCart looks joints up by name (leg_estimate.cpp:432-436): resolve the chain's names against the message's
@@ -1120,18 +1091,14 @@ public:
           exit(-1);
         }
     if (pb_legodo_set_chain(est->ctx, (int) model_->left_chain.size(), (int) model_->right_chain.size(), type.data(), row.data(), org.data(),
-                            axis.data(), use_torque_adjustment_ ? gain.data() : nullptr) != PB_OK) {
-      fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-      exit(1);
-    }
+                            axis.data(), use_torque_adjustment_ ? gain.data() : nullptr) != PB_OK)
+      pb_report_exit("LegOdoHandler", est->ctx);
     if (filter_joint_positions_ != 0) {
       // SimpleKalmanFilter(joint_process_noise, joint_observation_noise) (leg_estimate.cpp:56): the two values land in
       // process_noise_pos_ and process_noise_vel_, observation_noise_ keeps its default 5E-4 (simple_kalman_filter.hpp:15).
       // A new joint order (a new chain) starts the filters over.
-      if (pb_joint_filter_init(est->ctx, filter_joint_positions_, joint_process_noise_, joint_observation_noise_, 5E-4) != PB_OK) {
-        fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-        exit(1);
-      }
+      if (pb_joint_filter_init(est->ctx, filter_joint_positions_, joint_process_noise_, joint_observation_noise_, 5E-4) != PB_OK)
+        pb_report_exit("LegOdoHandler", est->ctx);
       // per-filter joint states: the filtered block [rows][B] and, for host messages, the two foot forces [2][B] behind it
       jf_pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(float) * (msg->joint_name.size() + 2) * (size_t) est->B);
     }
@@ -1187,6 +1154,16 @@ public:
     }
   };
 
+  // the measurement of `u` is still to be made from `lm`, into d_lo / d_mask: inside the pair kernel, or on its own (RBISIndexedMeasurement)
+  static void deferTo(RBISIndexedMeasurement *u, const std::shared_ptr<LegMsg> &lm, double *d_lo, uint8_t *d_mask)
+  {
+    u->pair_kernel = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *imu, bool keep) {
+      return lm->pair(ctx, imu, keep ? d_lo : nullptr, keep ? d_mask : nullptr);
+    };
+    u->make_measurement = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *ahead_of) {
+      return lm->odometry(ctx, ahead_of ? &ahead_of->imu_block : nullptr, nullptr, nullptr, d_lo, d_mask, nullptr, nullptr);
+    };
+  }
   // what the device-side entry points share: the pending-IMU decision, the odometry and the measurement LegOdoCommon forms
   // from its result
   RBISUpdateInterface *odometryUpdate(MavStateEstimator *est, std::shared_ptr<LegMsg> lm)
@@ -1205,27 +1182,20 @@ public:
     if (!legodo_ready_) initLegEstimate(est);
     if (sweep_dirty_) applySweep(est);
     if (control_contacts_dirty_) {
-      if (pb_legodo_set_control_contacts(est->ctx, n_control_contacts_, PB_HOST_BROADCAST) != PB_OK) fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
+      if (pb_legodo_set_control_contacts(est->ctx, n_control_contacts_, PB_HOST_BROADCAST) != PB_OK) pb_report("LegOdoHandler", est->ctx);
       control_contacts_dirty_ = false;
     }
-    bool fresh = false;
-    void *blk = pool_->get(fresh);
-    if (blk == nullptr) {
-      fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-      return nullptr;
-    }
-    auto block = std::make_shared<DeviceBlock>(pool_, blk);
-    double *d_lo = (double *) blk;
+    const std::shared_ptr<DeviceBlock> block = take_block(pool_);
+    if (!block) return pb_report("LegOdoHandler", est->ctx);
+    double *d_lo = (double *) block->p;
     uint8_t *d_mask = (uint8_t *) (d_lo + (size_t) 6 * B);   // lin_rate: z [3][B] | R diagonal [3][B] | mask [B]
     // LegOdoCommon::createMeasurement runs on the DEVICE for every mode (pb_legodo_set_measurement_mode): the increment, the status
     // and the position never cross PCIe.  A foot-state message has no pelvis position: mode pos_and_lin_rate then is the
     // reference's own fall-back to lin_rate (rbis_legodo_common.cpp:118-122) for every filter.
     const int dmode = (lc->mode_ == LegOdoCommon::MODE_LIN_AND_ROT_RATE) ? 1 : ((lc->mode_ == LegOdoCommon::MODE_POSITION_AND_LIN_RATE && lm->kind == 1) ? 2 : 0);
     if (dmode != device_meas_mode_) {
-      if (pb_legodo_set_measurement_mode(est->ctx, dmode, lc->R_legodo_xyz_, lc->R_legodo_vang_, lc->R_legodo_vang_uncertain_) != PB_OK) {
-        fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-        return nullptr;
-      }
+      if (pb_legodo_set_measurement_mode(est->ctx, dmode, lc->R_legodo_xyz_, lc->R_legodo_vang_, lc->R_legodo_vang_uncertain_) != PB_OK)
+        return pb_report("LegOdoHandler", est->ctx);
       device_meas_mode_ = dmode;
     }
     const bool lin = dmode == 0;
@@ -1233,43 +1203,20 @@ public:
     // the measurement can be made later, inside the step kernel, when its inputs outlive this call
     const bool defer = ahead != nullptr && one_kernel_pairs && lm->mem != PB_HOST;
     if (!defer) {
-      const int lrc = lm->odometry(est->ctx, ahead ? &ahead->imu_block : nullptr, nullptr, nullptr, d_lo, d_mask, nullptr, nullptr);
-      if (lrc != PB_OK) {
-        fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-        return nullptr;
-      }
+      if (lm->odometry(est->ctx, ahead ? &ahead->imu_block : nullptr, nullptr, nullptr, d_lo, d_mask, nullptr, nullptr) != PB_OK)
+        return pb_report("LegOdoHandler", est->ctx);
     }
     prev_legodo_utime_ = utime;
-    if (lin) {
-      auto *u = new RBISIndexedMeasurement(RBIS::velocityInds(), BatchArray(d_lo, PB_DEVICE), d_lo + (size_t) 3 * B, PB_R_DIAG, d_mask,
-                                           RBISUpdateInterface::legodo, utime);
-      u->owned_dev = block;
-      if (defer) {
-        u->pair_kernel = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *imu, bool keep) {
-          return lm->pair(ctx, imu, keep ? d_lo : nullptr, keep ? d_mask : nullptr);
-        };
-        u->make_measurement = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *ahead_of) {
-          return lm->odometry(ctx, ahead_of ? &ahead_of->imu_block : nullptr, nullptr, nullptr, d_lo, d_mask, nullptr, nullptr);
-        };
-      }
-      return u;
-    }
-    std::vector<int> idx;
-    {
+    std::vector<int> idx = RBIS::velocityInds();   // lin_rate: three rows
+    if (!lin) {
       double unused[6];
-      lc->getCovariance(lc->mode_, true, unused, &idx);
+      lc->getCovariance(lc->mode_, true, unused, &idx);   // (assigns idx: the six rows of the mode)
     }
-    auto *full = new RBISIndexedMeasurement(idx, BatchArray(d_lo, PB_DEVICE), d_lo + (size_t) 6 * B, PB_R_DIAG, d_mask, RBISUpdateInterface::legodo, utime);
+    // the block is z [m][B], then the diagonal of R [m][B], m = 3 or 6
+    auto *full = new RBISIndexedMeasurement(idx, BatchArray(d_lo, PB_DEVICE), d_lo + idx.size() * B, PB_R_DIAG, d_mask, RBISUpdateInterface::legodo, utime);
     full->owned_dev = block;
-    if (defer) {  // (the block holds the rows and masks of BOTH halves of mode 2's either-update)
-      full->pair_kernel = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *imu, bool keep) {
-        return lm->pair(ctx, imu, keep ? d_lo : nullptr, keep ? d_mask : nullptr);
-      };
-      full->make_measurement = [lm, d_lo, d_mask](pb_ctx *ctx, const RBISIMUProcessStep *ahead_of) {
-        return lm->odometry(ctx, ahead_of ? &ahead_of->imu_block : nullptr, nullptr, nullptr, d_lo, d_mask, nullptr, nullptr);
-      };
-    }
-    if (dmode == 1) return full;
+    if (defer) deferTo(full, lm, d_lo, d_mask);  // (the block holds the rows and masks of BOTH halves of mode 2's either-update)
+    if (dmode != 2) return full;
     // pos_and_lin_rate: the filters whose position is not valid take the lin_rate update on the velocity rows of the same block
     auto *fallback = new RBISIndexedMeasurement(RBIS::velocityInds(), BatchArray(d_lo + (size_t) 3 * B, PB_DEVICE), d_lo + (size_t) 9 * B, PB_R_DIAG,
                                                 d_mask + (size_t) B, RBISUpdateInterface::legodo, utime);
@@ -1284,10 +1231,7 @@ public:
   // the reference's handler (rbis_legodo_update.cpp:206-280)
   RBISUpdateInterface *processMessage(const msgs::joint_state_t *msg, MavStateEstimator *est)
   {
-    if (!force_torque_init_) {
-      fprintf(stdout, "Force/Torque message not received yet, not integrating leg odometry =========================\n");
-      return nullptr;
-    }
+    if (!forceTorqueSeen()) return nullptr;
     if (model_ == nullptr) {
       fprintf(stderr, "LegOdoHandler: a joint_state_t needs the robot model (construct the handler with a ModelClient)\n");
       exit(1);
@@ -1304,10 +1248,7 @@ public:
       if (!ff_pool_) ff_pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(float) * 2 * (size_t) est->B);
       bool fresh = false;
       void *blk = ff_pool_->get(fresh);
-      if (blk == nullptr || pb_memcpy_h2d(est->ctx, blk, forces, sizeof(float) * 2 * (size_t) est->B) != PB_OK) {
-        fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-        return nullptr;
-      }
+      if (blk == nullptr || pb_memcpy_h2d(est->ctx, blk, forces, sizeof(float) * 2 * (size_t) est->B) != PB_OK) return pb_report("LegOdoHandler", est->ctx);
       lm->forces_dev = std::make_shared<DeviceBlock>(ff_pool_, blk);
       forces = (const float *) blk;
       fmem = PB_DEVICE;
@@ -1344,19 +1285,12 @@ public:
         lm->own_f.assign((size_t) lm->rows + 2, 0.0f);
         out = lm->own_f.data();
       } else {
-        bool fresh = false;
-        void *blk = jf_pool_->get(fresh);
-        if (blk == nullptr) {
-          fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-          return nullptr;
-        }
-        lm->filtered = std::make_shared<DeviceBlock>(jf_pool_, blk);
-        out = (float *) blk;
+        lm->filtered = take_block(jf_pool_);
+        if (!lm->filtered) return pb_report("LegOdoHandler", est->ctx);
+        out = (float *) lm->filtered->p;
       }
-      if (pb_joint_filter(est->ctx, msg->utime, lm->rows, msg->joint_position, msg->joint_velocity, eff, msg->mem, out) != PB_OK) {
-        fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-        return nullptr;
-      }
+      if (pb_joint_filter(est->ctx, msg->utime, lm->rows, msg->joint_position, msg->joint_velocity, eff, msg->mem, out) != PB_OK)
+        return pb_report("LegOdoHandler", est->ctx);
       lm->jp = out;
       lm->je = nullptr;
       if (msg->mem == PB_HOST_BROADCAST) {
@@ -1367,10 +1301,7 @@ public:
         lm->ff = forces;
         if (msg->mem == PB_HOST) {  // the filtered joints are in HBM: the foot forces of a host message follow them there
           float *dff = out + (size_t) lm->rows * est->B;
-          if (pb_memcpy_h2d(est->ctx, dff, forces, sizeof(float) * 2 * (size_t) est->B) != PB_OK) {
-            fprintf(stderr, "LegOdoHandler: %s\n", pb_last_error(est->ctx));
-            return nullptr;
-          }
+          if (pb_memcpy_h2d(est->ctx, dff, forces, sizeof(float) * 2 * (size_t) est->B) != PB_OK) return pb_report("LegOdoHandler", est->ctx);
           lm->ff = dff;
           lm->mem = PB_DEVICE;
         }
@@ -1394,10 +1325,7 @@ public:
   // to lin_rate like the reference does while its world constraint is not initialised (rbis_legodo_common.cpp:118-122)
   RBISUpdateInterface *processMessageFeet(const msgs::foot_state_t *msg, MavStateEstimator *est)
   {
-    if (!force_torque_init_) {
-      fprintf(stdout, "Force/Torque message not received yet, not integrating leg odometry =========================\n");
-      return nullptr;
-    }
+    if (!forceTorqueSeen()) return nullptr;
     auto lm = std::make_shared<LegMsg>();
     lm->kind = 0;
     lm->mem = msg->feet.mem;
@@ -1417,10 +1345,7 @@ public:
   // from a finished increment (a caller that runs its own leg_estimate): createMeasurement and the handler's gates
   RBISUpdateInterface *processMessageDelta(const msgs::legodo_delta_t *msg, MavStateEstimator *est)
   {
-    if (!force_torque_init_) {
-      fprintf(stdout, "Force/Torque message not received yet, not integrating leg odometry =========================\n");
-      return nullptr;
-    }
+    if (!forceTorqueSeen()) return nullptr;
     // (:243-255) "Leg Odometry is not valid not integrating": no update and no decrement when no filter has a valid increment
     if (msg->delta_status != nullptr) {
       bool any = false;
@@ -1525,10 +1450,8 @@ public:
   {
     if (!ready_) {
       if (pb_yawlock_init(est->ctx, (int) mode, correction_period, yaw_slip_detect, yaw_slip_threshold_degrees, yaw_slip_disable_period,
-                          r_yaw_bias, r_yaw) != PB_OK) {
-        fprintf(stderr, "YawLockHandler: %s\n", pb_last_error(est->ctx));
-        exit(1);
-      }
+                          r_yaw_bias, r_yaw) != PB_OK)
+        pb_report_exit("YawLockHandler", est->ctx);
       pool_ = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, (sizeof(double) * 6 + 2) * (size_t) est->B);
       gyro_stride_ = est->B;
       ready_ = true;
@@ -1537,12 +1460,11 @@ public:
       fprintf(stderr, "YawLockHandler: joint positions must be PB_HOST_BROADCAST (one robot) or PB_DEVICE blocks\n");
       return nullptr;
     }
-    bool fresh = false;
-    void *blk = pool_->get(fresh);
-    if (blk == nullptr) return nullptr;
+    std::shared_ptr<DeviceBlock> block = take_block(pool_);
+    if (!block) return nullptr;
     const msgs_joint_ref j{ msg->joint_position, (int) msg->joint_name.size(), msg->mem };
     return new RBISYawLockUpdate((int) mode, j, is_robot_standing ? 1 : 0, body_gyro[2], bot_sq(bot_to_radians(r_yaw_bias)),
-                                 bot_sq(bot_to_radians(r_yaw)), std::make_shared<DeviceBlock>(pool_, blk), msg->utime);
+                                 bot_sq(bot_to_radians(r_yaw)), std::move(block), msg->utime);
   }
 
 private:
@@ -1557,14 +1479,32 @@ inline RBISIndexedMeasurement *makeIndexedMeasurement(const std::vector<int> &id
                                                       RBISUpdateInterface::sensor_enum sensor, int64_t utime)
 {
   if (z.mem == PB_DEVICE) return new RBISIndexedMeasurement(idx, z, cov_diag.data(), PB_R_DIAG_BROADCAST, mask, sensor, utime);
-  const size_t per = (z.mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
-  std::vector<double> zc(z.p, z.p + idx.size() * per);
-  std::vector<uint8_t> mc;
-  if (mask != nullptr && z.mem == PB_HOST) mc.assign(mask, mask + B);
-  auto *u = new RBISIndexedMeasurement(idx, std::move(zc), std::vector<double>(cov_diag), PB_R_DIAG_BROADCAST, std::move(mc), sensor,
-                                       utime);
-  u->measurement.mem = z.mem;
-  return u;
+  return hostIndexedMeasurement(idx, own_rows(z, idx.size(), B), cov_diag, PB_R_DIAG_BROADCAST, own_mask(mask, z.mem, B), z.mem, sensor, utime);
+}
+
+// What the processMessageInit of a pose sensor does to the state it initialises: the position rows and their covariance block
+// diag(cov_xyz) from pos [3][B] and, with `quat` [4][B], the quaternion and the chi block r_chi2 * I.  Host (or host-broadcast) arrays.
+// Filters with only[b] == 0 keep what they have; returns whether any filter was initialised.
+inline bool initPositionOrientation(RBIS &init_state, RBIM &init_cov, BatchArray pos, const double cov_xyz[3], const uint8_t *only = nullptr,
+                                    const double *quat = nullptr, double r_chi2 = 0.0)
+{
+  const int B = init_state.B;
+  const size_t per = batch_per(pos.mem, B);
+  bool any = false;
+  for (int b = 0; b < B; b++) {
+    if (only != nullptr && !only[b]) continue;
+    any = true;
+    const size_t sb = (per == 1) ? 0 : (size_t) b;
+    for (int i = 0; i < 3; i++) {
+      init_state(RBIS::position_ind + i, b) = pos.p[(size_t) i * per + sb];
+      for (int j = 0; j < 3; j++) {
+        init_cov(RBIS::position_ind + i, RBIS::position_ind + j, b) = (i == j) ? cov_xyz[i] : 0.0;
+        if (quat != nullptr) init_cov(RBIS::chi_ind + i, RBIS::chi_ind + j, b) = (i == j) ? r_chi2 : 0.0;
+      }
+    }
+    for (int i = 0; quat != nullptr && i < 4; i++) init_state.q(i, b) = quat[(size_t) i * per + sb];
+  }
+  return any;
 }
 
 class ScanMatcherHandler {
@@ -1623,17 +1563,11 @@ public:
       fprintf(stderr, "ScanMatcherHandler: *_yaw modes take host (or host-broadcast) pos/vel and orientation arrays\n");
       return nullptr;
     }
-    const size_t per = (omem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
+    const size_t per = batch_per(omem, B);
     std::vector<double> z((size_t) m * per, 0.0);
     if (mode != MODE_YAW) memcpy(z.data(), src.p, sizeof(double) * 3 * per);
-    std::vector<double> q(msg->orientation.p, msg->orientation.p + 4 * per);
-    std::vector<double> R(cov_scan_match);
-    std::vector<uint8_t> vmask;
-    if (msg->valid != nullptr && omem == PB_HOST) vmask.assign(msg->valid, msg->valid + B);
-    auto *u = new RBISIndexedPlusOrientationMeasurement(z_indices, std::move(z), std::move(R), PB_R_DIAG_BROADCAST, std::move(q),
-                                                        std::move(vmask), RBISUpdateInterface::scan_matcher, msg->utime);
-    u->measurement.mem = u->orientation.mem = omem;
-    return u;
+    return hostIndexedPlusOrientationMeasurement(z_indices, std::move(z), cov_scan_match, own_rows(msg->orientation, 4, B), own_mask(msg->valid, omem, B), omem,
+                                                 RBISUpdateInterface::scan_matcher, msg->utime);
   }
 };
 
@@ -1648,13 +1582,9 @@ public:
     if (msg->z_effective.mem == PB_DEVICE)
       return new RBISIndexedMeasurement(msg->z_indices, msg->z_effective, msg->R_effective, PB_R_FULL, nullptr, indexed_sensor,
                                         msg->utime);
-    const size_t per = (msg->z_effective.mem == PB_HOST_BROADCAST) ? 1 : (size_t) est->B;
-    std::vector<double> z(msg->z_effective.p, msg->z_effective.p + (size_t) m * per);
-    std::vector<double> R(msg->R_effective, msg->R_effective + (size_t) m * m * per);
-    auto *u = new RBISIndexedMeasurement(msg->z_indices, std::move(z), std::move(R), PB_R_FULL, std::vector<uint8_t>(),
-                                         indexed_sensor, msg->utime);
-    u->measurement.mem = u->cov_mem = msg->z_effective.mem;
-    return u;
+    const int mem = msg->z_effective.mem, B = est ? est->B : 1;   // (a host-only caller hands one robot's message over without an estimator)
+    return hostIndexedMeasurement(msg->z_indices, own_rows(msg->z_effective, (size_t) m, B), own_rows(BatchArray(msg->R_effective, mem), (size_t) m * m, B),
+                                  PB_R_FULL, {}, mem, indexed_sensor, msg->utime);
   }
   // processMessageInit (sensor_handlers.cpp:584-610): the measured entries and their covariance block initialise the
   // state; chi entries are folded into the quaternion (init_state.chiToQuat()).  Host messages only.
@@ -1664,7 +1594,7 @@ public:
   {
     if (msg->z_effective.mem == PB_DEVICE) return false;
     const int B = init_state.B, m = (int) msg->z_indices.size();
-    const size_t per = (msg->z_effective.mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
+    const size_t per = batch_per(msg->z_effective.mem, B);
     for (int b = 0; b < B; b++) {
       const size_t sb = (per == 1) ? 0 : (size_t) b;
       for (int ii = 0; ii < m; ii++) {
@@ -1680,10 +1610,9 @@ public:
       if (ang > chi_tol) {
         const double sh = sin(0.5 * ang) / ang, dq[4] = { cos(0.5 * ang), c[0] * sh, c[1] * sh, c[2] * sh };
         const double q0[4] = { init_state.q(0, b), init_state.q(1, b), init_state.q(2, b), init_state.q(3, b) };
-        init_state.q(0, b) = q0[0] * dq[0] - q0[1] * dq[1] - q0[2] * dq[2] - q0[3] * dq[3];
-        init_state.q(1, b) = q0[0] * dq[1] + q0[1] * dq[0] + q0[2] * dq[3] - q0[3] * dq[2];
-        init_state.q(2, b) = q0[0] * dq[2] - q0[1] * dq[3] + q0[2] * dq[0] + q0[3] * dq[1];
-        init_state.q(3, b) = q0[0] * dq[3] + q0[1] * dq[2] - q0[2] * dq[1] + q0[3] * dq[0];
+        double qn[4];
+        quat_mult(q0, dq, qn);
+        for (int i = 0; i < 4; i++) init_state.q(i, b) = qn[i];
         init_state(6, b) = init_state(7, b) = init_state(8, b) = 0.0;
       }
     }
@@ -1712,19 +1641,8 @@ public:
                           const RBIS & /*default_state*/, const RBIM & /*default_cov*/, RBIS &init_state, RBIM &init_cov)
   {
     if (msg->xyz_pos.mem == PB_DEVICE) return false;
-    const int B = init_state.B;
-    const size_t per = (msg->xyz_pos.mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
     init_state.utime = msg->utime;
-    bool any = false;
-    for (int b = 0; b < B; b++) {
-      if (msg->has_lock != nullptr && !msg->has_lock[b]) continue;
-      any = true;
-      for (int i = 0; i < 3; i++) {
-        init_state(RBIS::position_ind + i, b) = msg->xyz_pos.p[(size_t) i * per + (per == 1 ? 0 : (size_t) b)];
-        for (int j = 0; j < 3; j++) init_cov(RBIS::position_ind + i, RBIS::position_ind + j, b) = (i == j) ? cov_xyz[(size_t) i] : 0.0;
-      }
-    }
-    return any;
+    return initPositionOrientation(init_state, init_cov, msg->xyz_pos, cov_xyz.data(), msg->has_lock);
   }
 };
 
@@ -1768,18 +1686,11 @@ public:
     if (!to_body(msg, est->B, t, q, mask, mem)) return nullptr;
     const int m = (int) z_indices.size();
     const size_t per = t.size() / 3;
-    if (mode == MODE_POSITION) {
-      auto *u = new RBISIndexedMeasurement(z_indices, std::move(t), std::vector<double>(cov_vicon), PB_R_DIAG_BROADCAST, std::move(mask),
-                                           RBISUpdateInterface::vicon, msg->utime);
-      u->measurement.mem = mem;
-      return u;
-    }
+    if (mode == MODE_POSITION)
+      return hostIndexedMeasurement(z_indices, std::move(t), cov_vicon, PB_R_DIAG_BROADCAST, std::move(mask), mem, RBISUpdateInterface::vicon, msg->utime);
     std::vector<double> z((size_t) m * per, 0.0);  // entries at chi indices are ignored (rbis.cpp:203-205)
     if (mode == MODE_POSITION_ORIENT) memcpy(z.data(), t.data(), sizeof(double) * 3 * per);
-    auto *u = new RBISIndexedPlusOrientationMeasurement(z_indices, std::move(z), std::vector<double>(cov_vicon), PB_R_DIAG_BROADCAST,
-                                                        std::move(q), std::move(mask), RBISUpdateInterface::vicon, msg->utime);
-    u->measurement.mem = u->orientation.mem = mem;
-    return u;
+    return hostIndexedPlusOrientationMeasurement(z_indices, std::move(z), cov_vicon, std::move(q), std::move(mask), mem, RBISUpdateInterface::vicon, msg->utime);
   }
   bool processMessageInit(const msgs::rigid_transform_t *msg, const std::map<std::string, bool> & /*sensors_initialized*/,
                           const RBIS & /*default_state*/, const RBIM & /*default_cov*/, RBIS &init_state, RBIM &init_cov)
@@ -1787,22 +1698,10 @@ public:
     std::vector<double> t, q;
     std::vector<uint8_t> mask;
     int mem;
-    const int B = init_state.B;
-    if (!to_body(msg, B, t, q, mask, mem, /*for_init=*/true)) return false;
-    const size_t per = t.size() / 3;
+    if (!to_body(msg, init_state.B, t, q, mask, mem, /*for_init=*/true)) return false;
     init_state.utime = msg->utime;
-    for (int b = 0; b < B; b++) {
-      const size_t sb = per == 1 ? 0 : (size_t) b;
-      for (int i = 0; i < 3; i++) {
-        init_state(RBIS::position_ind + i, b) = t[(size_t) i * per + sb];
-        for (int j = 0; j < 3; j++) {
-          init_cov(RBIS::position_ind + i, RBIS::position_ind + j, b) = (i == j) ? r_xyz2 : 0.0;
-          init_cov(RBIS::chi_ind + i, RBIS::chi_ind + j, b) = (i == j) ? r_chi2 : 0.0;
-        }
-      }
-      for (int i = 0; i < 4; i++) init_state.q(i, b) = q[(size_t) i * per + sb];
-    }
-    return true;
+    const double cov_xyz[3] = { r_xyz2, r_xyz2, r_xyz2 };
+    return initPositionOrientation(init_state, init_cov, BatchArray(t.data(), mem), cov_xyz, nullptr, q.data(), r_chi2);
   }
 private:
   // msg -> body pose per filter; mask 0 where |translation| < 1e-5 on all axes (":493-494 return NULL")
@@ -1814,7 +1713,7 @@ private:
       fprintf(stderr, "ViconHandler: host (or host-broadcast) trans and quat arrays expected\n");
       return false;
     }
-    const size_t per = (mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
+    const size_t per = batch_per(mem, B);
     t.resize(3 * per);
     q.resize(4 * per);
     bool any = false;
@@ -1826,11 +1725,7 @@ private:
       if (apply_frame) {
         bot_quat_rotate_to(qv, body_to_vicon.trans_vec, tb);
         for (int i = 0; i < 3; i++) tb[i] += tv[i];
-        const double *a = qv, *c = body_to_vicon.rot_quat;
-        qb[0] = a[0] * c[0] - a[1] * c[1] - a[2] * c[2] - a[3] * c[3];
-        qb[1] = a[0] * c[1] + a[1] * c[0] + a[2] * c[3] - a[3] * c[2];
-        qb[2] = a[0] * c[2] - a[1] * c[3] + a[2] * c[0] + a[3] * c[1];
-        qb[3] = a[0] * c[3] + a[1] * c[2] - a[2] * c[1] + a[3] * c[0];
+        quat_mult(qv, body_to_vicon.rot_quat, qb);
       }
       const bool dropped = !for_init && fabs(tv[0]) < 1e-5 && fabs(tv[1]) < 1e-5 && fabs(tv[2]) < 1e-5;
       if (per > 1) mask[b] = !dropped;
@@ -1878,7 +1773,8 @@ public:
       fprintf(stderr, "PoseMeasHandler: host (or host-broadcast) pos and orientation arrays expected\n");
       return nullptr;
     }
-    const size_t per = (mem == PB_HOST_BROADCAST) ? 1 : (size_t) est->B;
+    const int B = est ? est->B : 1;   // (a host-only caller hands one robot's message over without an estimator)
+    const size_t per = batch_per(mem, B);
     // a pose at the origin is "no pose" (:74-75), per filter: mask
     std::vector<uint8_t> mask;
     if (per > 1) mask.assign(per, 1);
@@ -1889,41 +1785,22 @@ public:
       any = any || !dropped;
     }
     if (!any) return nullptr;
-    std::vector<double> t(msg->pos.p, msg->pos.p + 3 * per);
-    if (mode == MODE_POSITION) {
-      auto *u = new RBISIndexedMeasurement(z_indices, std::move(t), std::vector<double>(cov_pose_meas), PB_R_DIAG_BROADCAST, std::move(mask),
-                                           RBISUpdateInterface::pose_meas, msg->utime);
-      u->measurement.mem = mem;
-      return u;
-    }
+    if (mode == MODE_POSITION)
+      return hostIndexedMeasurement(z_indices, own_rows(msg->pos, 3, B), cov_pose_meas, PB_R_DIAG_BROADCAST, std::move(mask), mem, RBISUpdateInterface::pose_meas,
+                                    msg->utime);
     std::vector<double> z(6 * per, 0.0);  // entries at chi indices are ignored (rbis.cpp:203-205)
-    memcpy(z.data(), t.data(), sizeof(double) * 3 * per);
-    std::vector<double> q(msg->orientation.p, msg->orientation.p + 4 * per);
-    auto *u = new RBISIndexedPlusOrientationMeasurement(z_indices, std::move(z), std::vector<double>(cov_pose_meas), PB_R_DIAG_BROADCAST,
-                                                        std::move(q), std::move(mask), RBISUpdateInterface::pose_meas, msg->utime);
-    u->measurement.mem = u->orientation.mem = mem;
-    return u;
+    memcpy(z.data(), msg->pos.p, sizeof(double) * 3 * per);
+    return hostIndexedPlusOrientationMeasurement(z_indices, std::move(z), cov_pose_meas, own_rows(msg->orientation, 4, B), std::move(mask), mem,
+                                                 RBISUpdateInterface::pose_meas, msg->utime);
   }
   // :98-129
   bool processMessageInit(const msgs::pose_t *msg, const std::map<std::string, bool> & /*sensors_initialized*/,
                           const RBIS & /*default_state*/, const RBIM & /*default_cov*/, RBIS &init_state, RBIM &init_cov)
   {
-    const int mem = msg->pos.mem, B = init_state.B;
-    if (mem == PB_DEVICE || msg->orientation.mem != mem) return false;
-    const size_t per = (mem == PB_HOST_BROADCAST) ? 1 : (size_t) B;
+    if (msg->pos.mem == PB_DEVICE || msg->orientation.mem != msg->pos.mem) return false;
     init_state.utime = msg->utime;
-    for (int b = 0; b < B; b++) {
-      const size_t sb = per == 1 ? 0 : (size_t) b;
-      for (int i = 0; i < 3; i++) {
-        init_state(RBIS::position_ind + i, b) = msg->pos.p[(size_t) i * per + sb];
-        for (int j = 0; j < 3; j++) {
-          init_cov(RBIS::position_ind + i, RBIS::position_ind + j, b) = (i == j) ? r_xyz2 : 0.0;
-          init_cov(RBIS::chi_ind + i, RBIS::chi_ind + j, b) = (i == j) ? r_chi2 : 0.0;
-        }
-      }
-      for (int i = 0; i < 4; i++) init_state.q(i, b) = msg->orientation.p[(size_t) i * per + sb];
-    }
-    return true;
+    const double cov_xyz[3] = { r_xyz2, r_xyz2, r_xyz2 };
+    return initPositionOrientation(init_state, init_cov, msg->pos, cov_xyz, nullptr, msg->orientation.p, r_chi2);
   }
 };
 
@@ -1995,15 +1872,11 @@ public:
     if (mode == MODE_VELOCITY) {
       if (msg->translation.mem == PB_DEVICE) return nullptr;
       const double elapsed = (double) (msg->timestamp - msg->prev_timestamp) * 1E-6;
-      const bool bcast = msg->translation.mem == PB_HOST_BROADCAST;
-      std::vector<double> z((size_t) 3 * (bcast ? 1 : B));
-      for (size_t i = 0; i < z.size(); i++) z[i] = msg->translation.p[i] / elapsed;
-      std::vector<uint8_t> mask;
-      if (msg->estimate_valid && !bcast) mask.assign(msg->estimate_valid, msg->estimate_valid + B);
-      auto *u = new RBISIndexedMeasurement(RBIS::velocityInds(), std::move(z), std::vector<double>(cov_fovis), PB_R_DIAG_BROADCAST,
-                                           std::move(mask), RBISUpdateInterface::fovis, msg->timestamp);
-      if (bcast) u->measurement.mem = PB_HOST_BROADCAST;
-      return u;
+      const int mem = msg->translation.mem;
+      std::vector<double> z = own_rows(msg->translation, 3, B);
+      for (double &v : z) v /= elapsed;
+      return hostIndexedMeasurement(RBIS::velocityInds(), std::move(z), cov_fovis, PB_R_DIAG_BROADCAST, own_mask(msg->estimate_valid, mem, B), mem,
+                                    RBISUpdateInterface::fovis, msg->timestamp);
     }
     // position / position_orient: T1 = T0(posterior at prev_timestamp) * (t, q).  T0 comes from a checkpoint (history) or
     // from the snapshot markKeyframe() took, never from the head: updates the estimator is holding back for fusion
@@ -2044,22 +1917,16 @@ public:
     // must not overwrite it, because the history re-applies the update when an older measurement arrives late.
     if (!pool) pool = std::make_shared<DevicePool>(est->ctx, est->ctx_alive, sizeof(double) * 10 * (size_t) B + (size_t) B);
     bool fresh = false;
-    void *blk = pool->get(fresh);
-    if (blk == nullptr) {
-      fprintf(stderr, "FovisHandler: %s\n", pb_last_error(est->ctx));
-      return nullptr;
-    }
-    auto block = std::make_shared<DeviceBlock>(pool, blk);
-    double *d_z6 = (double *) blk, *d_q = d_z6 + (size_t) 6 * B;
+    const std::shared_ptr<DeviceBlock> block = take_block(pool, &fresh);
+    if (!block) return pb_report("FovisHandler", est->ctx);
+    double *d_z6 = (double *) block->p, *d_q = d_z6 + (size_t) 6 * B;
     uint8_t *d_valid = (uint8_t *) (d_q + (size_t) 4 * B);
     if (fresh) {  // rows 3..5 of z are never written again: z at chi indices is ignored (rbis.cpp:203-205)
       std::vector<double> zero((size_t) 6 * B, 0.0);
       pb_memcpy_h2d(est->ctx, d_z6, zero.data(), sizeof(double) * 6 * B);
     }
-    if (pb_compose_delta(est->ctx, slot, msg->translation.p, msg->rotation.p, d_z6, d_q, msg->translation.mem) != PB_OK) {
-      fprintf(stderr, "FovisHandler: %s\n", pb_last_error(est->ctx));
-      return nullptr;
-    }
+    if (pb_compose_delta(est->ctx, slot, msg->translation.p, msg->rotation.p, d_z6, d_q, msg->translation.mem) != PB_OK)
+      return pb_report("FovisHandler", est->ctx);
     const uint8_t *valid = nullptr;  // the composed z / q live on the device, so does the mask that goes with them
     if (msg->estimate_valid != nullptr && msg->translation.mem != PB_HOST_BROADCAST) {  // broadcast: all valid here
       pb_memcpy_h2d(est->ctx, d_valid, msg->estimate_valid, (size_t) B);
@@ -2234,7 +2101,7 @@ public:
     if (!ready_) {
       const int rc0 = pb_score_init(est->ctx, time_elapsed_threshold, distance_threshold);
       if (rc0 != PB_OK) {  // (a negative threshold key, or no memory: the message is refused, the estimator goes on)
-        fprintf(stderr, "DriftPerDistance: %s\n", pb_last_error(est->ctx));
+        pb_report("DriftPerDistance", est->ctx);
         est->last_status = rc0;
         return;
       }

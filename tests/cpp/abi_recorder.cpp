@@ -1,11 +1,12 @@
 // abi_recorder.cpp -- a recording stand-in for the C ABI functions (include/pronto_batch.h) that the estimator core and the
-// update objects of pronto_amd/csrc/mav_state_est.hpp call.  No HIP, no device: every call appends ONE line to stdout -- the
+// update objects of pronto_amd/csrc/mav_state_est.hpp, and the sensor handlers of mav_state_est_batch.hpp, call.  No HIP, no device: every call appends ONE line to stdout -- the
 // function's name, every scalar argument, index lists in full -- so that a trace is the list of decisions the estimator took.
 // Pointer arguments are logged by kind, never as an address:
 //     NULL | host:<FNV-1a of exactly the bytes the real call would read> | dev#<ordinal of its pb_malloc>+<byte offset> | out
 // ("out" = a host buffer the call fills).  The recorder models only what the estimator reads back: pb_head_slot (follows
 // pb_set_output_slot / every update / pb_state_restore / pb_reset as the library does), pb_batch, pb_n_states, pb_mask_count (an
-// answer the driver sets) and pb_get_head (a deterministic pattern).  rec_fail_call() makes the k-th call of a named function
+// answer the driver sets), pb_get_head and the other host outputs a handler reads (pb_imu_notch / _counts with PB_HOST, pb_joint_filter
+// for a broadcast message, pb_score_get / _last / _best): a deterministic pattern.  rec_fail_call() makes the k-th call of a named function
 // return PB_ERR_HIP, which is how tests/cpp/estimator_trace.cpp reaches the error paths.
 #include <cinttypes>
 #include <cstdarg>
@@ -22,12 +23,16 @@
 struct pb_ctx {
   int n, B, nhist = 0;
   int out_slot = -1, pred_slot = -1, head_slot = -1;
-  int gets = 0;
+  int gets = 0, fills = 0;
 };
 
 namespace {
 struct DevBlock { const char *base; size_t bytes; int ordinal; };
-std::vector<DevBlock> g_blocks;
+// (a block nobody pb_free'd shows in the trace as a missing pb_free line; its stand-in memory goes back at exit, so that a sanitized build
+// can record such a trace)
+struct DevBlocks : std::vector<DevBlock> {
+  ~DevBlocks() { for (const DevBlock &d : *this) free((void *) d.base); }
+} g_blocks;
 int g_ordinal = 0, g_mask_count = 1;
 std::map<std::string, int> g_fail_in;   // function -> calls left until the failing one
 std::string g_error = "no error";
@@ -67,6 +72,16 @@ std::string list(const int *idx, int m)
   return s + "]";
 }
 const char *out(const void *p) { return p ? "out" : "NULL"; }
+std::string flt(const pb_ctx *c, const float *p, int mem, int rows) { return ptr(p, mem, sizeof(float) * rows * (mem == PB_HOST_BROADCAST ? 1 : c->B)); }
+// an output that is a pb_malloc'ed block (logged as such) or a host buffer the call fills
+std::string dst(const void *p) { return p == nullptr ? "NULL" : ptr(p, PB_DEVICE, 0) == "dev:foreign" ? "out" : ptr(p, PB_DEVICE, 0); }
+// the pattern of a filled host output: differs from call to call and from entry to entry
+template <class T> void pattern(pb_ctx *c, T *o, size_t k, const int32_t *only_where = nullptr, size_t B = 1)
+{
+  const double base = 0.5 * ++c->fills;
+  for (size_t i = 0; o && i < k; i++)
+    if (only_where == nullptr || only_where[i % B] > 0) o[i] = (T) (base + 0.03125 * (double) i);
+}
 
 // logs the line; returns PB_ERR_HIP when this call is the one rec_fail_call() named
 int call(const char *fn, const char *fmt, ...)
@@ -98,6 +113,7 @@ int updated(pb_ctx *c, int rc)
 
 void rec_fail_call(const char *fn, int kth) { g_fail_in[fn] = kth; }
 void rec_set_mask_count(int count) { g_mask_count = count; }
+std::string rec_ptr(const void *p, int mem, size_t host_bytes) { return ptr(p, mem, host_bytes); }
 
 #define S(x) (x).c_str()
 
@@ -258,5 +274,147 @@ int pb_smooth_step(pb_ctx *, int next_pred, int next, int cur, int o, double dt)
 int pb_smooth_step_masked(pb_ctx *c, int next_pred, int next, int cur, int o, double dt, const uint8_t *step, int mem)
 {
   return call("pb_smooth_step_masked", " next_pred=%d next=%d cur=%d out=%d dt=%.17g step=%s mem=%d", next_pred, next, cur, o, dt, S(msk(c, step, mem)), mem);
+}
+// ---- what the sensor handlers (mav_state_est_batch.hpp) call ----
+int pb_memcpy_h2d(pb_ctx *, void *d, const void *src, uint64_t bytes)
+{
+  return call("pb_memcpy_h2d", " dst=%s src=%s bytes=%" PRIu64, S(dst(d)), S(ptr(src, PB_HOST, (size_t) bytes)), bytes);
+}
+int pb_compose_delta(pb_ctx *c, int slot, const double *t, const double *q, double *z_out, double *quat_out, int mem)
+{
+  return call("pb_compose_delta", " slot=%d t=%s q=%s z_out=%s quat_out=%s mem=%d", slot, S(dbl(c, t, mem, 3)), S(dbl(c, q, mem, 4)), S(dst(z_out)),
+              S(dst(quat_out)), mem);
+}
+int pb_imu_notch_init(pb_ctx *, double f, double fs) { return call("pb_imu_notch_init", " notch_freq=%.17g fs=%.17g", f, fs); }
+int pb_imu_notch(pb_ctx *c, int n_packets, const double *acc, double *o, int mem)
+{
+  const int rc = call("pb_imu_notch", " n_packets=%d accel=%s out=%s mem=%d", n_packets, S(dbl(c, acc, mem, 3 * n_packets)), S(dst(o)), mem);
+  if (rc == PB_OK && mem == PB_HOST) pattern(c, o, (size_t) 3 * c->B);
+  return rc;
+}
+int pb_imu_notch_counts(pb_ctx *c, int max_packets, const int32_t *counts, const double *acc, double *o, int mem)
+{
+  const int rc = call("pb_imu_notch_counts", " max_packets=%d counts=%s accel=%s out=%s mem=%d", max_packets, S(ptr(counts, mem, sizeof(int32_t) * c->B)),
+                      S(dbl(c, acc, mem, 3 * max_packets)), S(dst(o)), mem);
+  if (rc == PB_OK && mem == PB_HOST) pattern(c, o, (size_t) 3 * c->B, counts, (size_t) c->B);   // a filter without a new packet is not written
+  return rc;
+}
+int pb_ins_body_block(pb_ctx *c, const double *gyro, const double *accel, const double *raw_dt, const int64_t *utimes, int64_t utime, const uint8_t *valid,
+                      const double rot_quat[4], const double trans_vec[3], double dt_default, int dt_from_utimes, int mem, double *o, uint8_t *valid_out)
+{
+  return call("pb_ins_body_block", " gyro=%s accel=%s raw_dt=%s utimes=%s utime=%" PRId64 " valid=%s rot=%s trans=%s dt=%.17g dt_from_utimes=%d mem=%d out=%s valid_out=%s",
+              S(dbl(c, gyro, mem, 3)), S(dbl(c, accel, mem, 3)), S(dbl(c, raw_dt, mem, 1)), S(ptr(utimes, mem, sizeof(int64_t) * c->B)), utime, S(msk(c, valid, mem)),
+              S(host(rot_quat, 4 * sizeof(double))), trans_vec ? S(host(trans_vec, 3 * sizeof(double))) : "NULL", dt_default, dt_from_utimes, mem, S(dst(o)),
+              S(dst(valid_out)));
+}
+int pb_legodo_init(pb_ctx *, double lt, double ht, int64_t ld, int64_t hd, int fce)
+{
+  return call("pb_legodo_init", " low=%.17g high=%.17g low_delay=%" PRId64 " high_delay=%" PRId64 " filter_contact_events=%d", lt, ht, ld, hd, fce);
+}
+int pb_legodo_set_contact_mode(pb_ctx *, int standing, double total_force, double level, int ctrl)
+{
+  return call("pb_legodo_set_contact_mode", " standing=%d total_force=%.17g level=%.17g use_controller_input=%d", standing, total_force, level, ctrl);
+}
+int pb_legodo_set_zero_initial_velocity(pb_ctx *, int ticks) { return call("pb_legodo_set_zero_initial_velocity", " ticks=%d", ticks); }
+int pb_legodo_set_measurement_mode(pb_ctx *, int mode, double r_xyz, double r_vang, double r_vang_u)
+{
+  return call("pb_legodo_set_measurement_mode", " mode=%d r_xyz=%.17g r_vang=%.17g r_vang_uncertain=%.17g", mode, r_xyz, r_vang, r_vang_u);
+}
+int pb_legodo_set_param_block(pb_ctx *c, const double *block, int mem) { return call("pb_legodo_set_param_block", " block=%s mem=%d", S(dbl(c, block, mem, PB_LEGPAR_ROWS)), mem); }
+int pb_legodo_set_control_contacts(pb_ctx *c, const int32_t *n, int mem)
+{
+  return call("pb_legodo_set_control_contacts", " n_contacts=%s mem=%d", S(ptr(n, mem, sizeof(int32_t) * 2 * (mem == PB_HOST_BROADCAST ? 1 : c->B))), mem);
+}
+int pb_legodo_set_message_times(pb_ctx *c, const int64_t *utimes, const uint8_t *valid, int mem)
+{
+  return call("pb_legodo_set_message_times", " utimes=%s valid=%s mem=%d", S(ptr(utimes, mem, sizeof(int64_t) * c->B)), S(msk(c, valid, mem)), mem);
+}
+int pb_legodo_set_chain(pb_ctx *, int n_left, int n_right, const int *type, const int *row, const double *org, const double *axis, const float *gain)
+{
+  const int k = n_left + n_right;
+  return call("pb_legodo_set_chain", " n_left=%d n_right=%d type=%s row=%s origin=%s axis=%s gain=%s", n_left, n_right, S(list(type, k)), S(list(row, k)),
+              S(host(org, sizeof(double) * 6 * k)), S(host(axis, sizeof(double) * 3 * k)), gain ? S(host(gain, sizeof(float) * k)) : "NULL");
+}
+int pb_legodo_update(pb_ctx *c, int64_t utime, const double *feet, const double *forces, int mem, int zero_delta, double r, double ru, double *o_delta,
+                     double *o_status, double *lo, uint8_t *mask)
+{
+  return call("pb_legodo_update", " utime=%" PRId64 " feet=%s forces=%s mem=%d zero_delta=%d r=%.17g ru=%.17g delta_out=%s status_out=%s lo_out=%s mask_out=%s", utime,
+              S(dbl(c, feet, mem, 14)), S(dbl(c, forces, mem, 2)), mem, zero_delta, r, ru, S(dst(o_delta)), S(dst(o_status)), S(dst(lo)), S(dst(mask)));
+}
+int pb_legodo_update_after_predict(pb_ctx *c, const double *imu, int imu_mem, int64_t utime, const double *feet, const double *forces, int mem, int zero_delta,
+                                   double r, double ru, double *o_delta, double *o_status, double *lo, uint8_t *mask)
+{
+  return call("pb_legodo_update_after_predict", " imu=%s imu_mem=%d utime=%" PRId64 " feet=%s forces=%s mem=%d zero_delta=%d r=%.17g ru=%.17g delta_out=%s status_out=%s lo_out=%s mask_out=%s",
+              S(dbl(c, imu, imu_mem, 7)), imu_mem, utime, S(dbl(c, feet, mem, 14)), S(dbl(c, forces, mem, 2)), mem, zero_delta, r, ru, S(dst(o_delta)), S(dst(o_status)),
+              S(dst(lo)), S(dst(mask)));
+}
+int pb_legodo_update_joints(pb_ctx *c, const double *imu, int imu_mem, int64_t utime, int n_rows, const float *jp, const float *je, const float *forces, int mem,
+                            int zero_delta, double r, double ru, double *o_delta, double *o_status, double *lo, uint8_t *mask, double *o_pos, uint8_t *o_pos_ok)
+{
+  return call("pb_legodo_update_joints", " imu=%s imu_mem=%d utime=%" PRId64 " n_rows=%d position=%s effort=%s forces=%s mem=%d zero_delta=%d r=%.17g ru=%.17g delta_out=%s status_out=%s lo_out=%s mask_out=%s position_out=%s position_status_out=%s",
+              S(dbl(c, imu, imu_mem, 7)), imu_mem, utime, n_rows, S(flt(c, jp, mem, n_rows)), S(flt(c, je, mem, n_rows)), S(flt(c, forces, mem, 2)), mem, zero_delta, r, ru,
+              S(dst(o_delta)), S(dst(o_status)), S(dst(lo)), S(dst(mask)), S(dst(o_pos)), S(dst(o_pos_ok)));
+}
+int pb_step_legodo_joints(pb_ctx *c, const double *imu, int imu_mem, const double q[4], int64_t utime, int n_rows, const float *jp, const float *je,
+                          const float *forces, int mem, double r, double ru, double *lo, uint8_t *mask)
+{
+  return updated(c, call("pb_step_legodo_joints", " imu=%s imu_mem=%d q=%s utime=%" PRId64 " n_rows=%d position=%s effort=%s forces=%s mem=%d r=%.17g ru=%.17g lo_out=%s mask_out=%s",
+                         S(dbl(c, imu, imu_mem, 7)), imu_mem, S(host(q, 4 * sizeof(double))), utime, n_rows, S(flt(c, jp, mem, n_rows)), S(flt(c, je, mem, n_rows)),
+                         S(flt(c, forces, mem, 2)), mem, r, ru, S(dst(lo)), S(dst(mask))));
+}
+int pb_step_legodo_feet(pb_ctx *c, const double *imu, int imu_mem, const double q[4], int64_t utime, const double *feet, const double *forces, int mem, double r,
+                        double ru, double *lo, uint8_t *mask)
+{
+  return updated(c, call("pb_step_legodo_feet", " imu=%s imu_mem=%d q=%s utime=%" PRId64 " feet=%s forces=%s mem=%d r=%.17g ru=%.17g lo_out=%s mask_out=%s", S(dbl(c, imu, imu_mem, 7)),
+                         imu_mem, S(host(q, 4 * sizeof(double))), utime, S(dbl(c, feet, mem, 14)), S(dbl(c, forces, mem, 2)), mem, r, ru, S(dst(lo)), S(dst(mask))));
+}
+int pb_joint_filter_init(pb_ctx *, int mode, double pp, double pv, double on)
+{
+  return call("pb_joint_filter_init", " mode=%d process_noise_pos=%.17g process_noise_vel=%.17g observation_noise=%.17g", mode, pp, pv, on);
+}
+int pb_joint_filter(pb_ctx *c, int64_t utime, int n_rows, const float *jp, const float *jv, const float *je, int mem, float *o)
+{
+  const int rc = call("pb_joint_filter", " utime=%" PRId64 " n_rows=%d position=%s velocity=%s effort=%s mem=%d out=%s", utime, n_rows, S(flt(c, jp, mem, n_rows)),
+                      S(flt(c, jv, mem, n_rows)), S(flt(c, je, mem, n_rows)), mem, S(dst(o)));
+  if (rc == PB_OK && mem == PB_HOST_BROADCAST) pattern(c, o, (size_t) n_rows);   // (per-filter messages are filtered into a device block)
+  return rc;
+}
+int pb_yawlock_init(pb_ctx *, int mode, int period, int slip, double thr, double disable, double r_bias, double r_yaw)
+{
+  return call("pb_yawlock_init", " mode=%d correction_period=%d yaw_slip_detect=%d threshold=%.17g disable_period=%.17g r_yaw_bias=%.17g r_yaw=%.17g", mode, period, slip, thr,
+              disable, r_bias, r_yaw);
+}
+int pb_score_init(pb_ctx *, double t, double d) { return call("pb_score_init", " time_threshold=%.17g distance_threshold=%.17g", t, d); }
+int pb_score_ground_truth(pb_ctx *c, int64_t utime, const int64_t *utimes, const double *pose7, const uint8_t *valid, int slot, int flags, int mem)
+{
+  return call("pb_score_ground_truth", " utime=%" PRId64 " utimes=%s pose7=%s valid=%s slot=%d flags=%d mem=%d", utime, S(ptr(utimes, mem, sizeof(int64_t) * c->B)),
+              S(dbl(c, pose7, mem, 7)), S(msk(c, valid, mem)), slot, flags, mem);
+}
+int pb_score_get(pb_ctx *c, int first, int count, double *rows_out, int64_t *counts_out, int mem)
+{
+  const int rc = call("pb_score_get", " first=%d count=%d rows=%s counts=%s mem=%d", first, count, S(dst(rows_out)), S(dst(counts_out)), mem);
+  if (rc == PB_OK && mem == PB_HOST) {
+    pattern(c, rows_out, (size_t) PB_SCORE_ROWS * count);
+    pattern(c, counts_out, (size_t) PB_SCORE_COUNTS * count);
+  }
+  return rc;
+}
+// no window yet for the first question, then a window that closes with every second one
+int pb_score_last(pb_ctx *c, int filter, int64_t *utime, double o[10])
+{
+  const int rc = call("pb_score_last", " filter=%d utime=out out=out", filter);
+  if (rc != PB_OK) return rc;
+  c->gets++;
+  *utime = c->gets < 2 ? -2 : 1000 * (int64_t) (c->gets / 2);
+  pattern(c, o, 10);
+  return PB_OK;
+}
+int pb_score_best(pb_ctx *c, int metric, int *filter_out, double *value_out)
+{
+  const int rc = call("pb_score_best", " metric=%d filter=out value=%s", metric, out(value_out));
+  if (rc != PB_OK) return rc;
+  *filter_out = metric % c->B;
+  pattern(c, value_out, value_out ? 1 : 0);
+  return PB_OK;
 }
 }  // extern "C"
