@@ -1,7 +1,8 @@
 // pb_ctx.hpp -- the context behind the C ABI, the owner of its device memory (dev_alloc / dev_release) and what crosses the translation
 // units of libpronto_batch.so: the per-call guard, the input resolver and the launchers.  It includes the
 // argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp), never a kernel: each .hip
-// includes the kernel headers it launches from, so every kernel is compiled in one object.
+// includes the kernel headers it launches from, so every kernel is compiled in one object.  WHICH kernel a launcher runs is decided in
+// pb_policy.hpp (host-only, tested on the CPU): the context keeps one Policy, made in pb_create.
 // (the kernels are instantiated in twenty-one objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
 // pb_step_corr_pred.hip, pb_step_leg.hip and pb_legpar.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
 // pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
@@ -21,6 +22,7 @@
 #include <vector>
 
 #include "../../include/pronto_batch.h"
+#include "pb_policy.hpp"
 #include "rbis_tile_io.hpp"
 #include "rbis_coop.hpp"
 #include "rbis_legodo.hpp"
@@ -113,16 +115,7 @@ struct pb_ctx {
   Consts k{ 9.80665, 1e-6 };
   int64_t utime = 0;
   bool have_state = false;
-  bool half15 = false;  // the 15-state fused step with two workgroups per tile (pb_create: batches that leave half the workgroup slots empty; PRONTO_BATCH_HALF=0/1)
-  bool replay_onelane = false;  // pb_replay_legodo_fused on the first, one-lane-per-filter kernel (15 states; PRONTO_BATCH_REPLAY_ONELANE=1, read by pb_create as every other switch)
-  bool coop15 = false;  // PRONTO_BATCH_COOP15=1: run the 15-state step on the two-wave cooperative kernel (A/B switch)
-  int mem_hint = 0;     // MH_* cache policy of the step kernels' state round trip (PRONTO_BATCH_MEMHINT=0/1/2 forces it)
-  // pb_run_legodo's cache-blocked order (filter range outer, time inner) for states beyond the memory-side cache: filters per block
-  // (whole tiles; 0 = the whole batch per launch), and the kernel / cache policy that block size wants
-  int run_block = 0, run_block_hint = 0;
-  bool run_block_coop15 = false;
-  bool quad21 = true;   // PRONTO_BATCH_QUAD21=0: run the 21-state step on the two-wave kernel instead of the four-wave one (A/B)
-  bool generic_update = false;  // PRONTO_BATCH_GENERIC_UPDATE=1: every stand-alone update on the run-time-index kernel (A/B, tests)
+  Policy policy;  // which kernel, grid shape and cache policy this context runs (pb_policy.hpp; made once, in pb_create)
   bool smooth_attr = false;  // dynamic-LDS limit of the smoother kernels raised on this device
   bool smooth_wide_attr = false;
   int n_cu = 256;            // compute units of the device (grid of the persistent smoother kernel)
@@ -206,7 +199,7 @@ inline void update_done(pb_ctx *c, double *target)
 
 #define LAUNCHCHK(c) HIPCHK((c), hipGetLastError())
 
-// the cache policy of the state round trip (MemHint, chosen in pb_create from the state size) as a compile-time constant: f(MH)
+// the cache policy of the state round trip (MemHint; Policy::mem_hint) as a compile-time constant: f(MH)
 template <class F>
 static void with_mem_hint(int mem_hint, F f)
 {
@@ -341,7 +334,7 @@ int pbk_idle_restore(pb_ctx *c, double *out, double *pred, const double q[4]);
 int pbk_step(pb_ctx *c, bool update, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
              const StepBcast *bcast = nullptr);  // bcast: one message for every filter, as kernel arguments
 // the fused step on the filters [b0, b0 + nb) only (whole tiles, in place; pb_run_legodo's cache-blocked order)
-int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, bool coop15, int mem_hint);
+int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, Mapping map, int mem_hint);
 // IMU step + leg odometry (from `lin`) + its lin_rate update in ONE kernel; -1 = this context has no such kernel (run
 // pb_legodo_update* ahead of pbk_step instead)
 // mp.mode 1 / 2: LegOdoCommon's six-row measurements instead (lo_out [12][B], mask_out [2][B] as pb_legodo_set_measurement_mode)
@@ -368,23 +361,28 @@ int pbk_step_corr_pred_kernel(pb_ctx *c, int corr_kind, double *out, double *pre
 int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *lo, const uint8_t *mask, const double q[4],
                      const double *z2, const double *r2, const double *rb2, const double *qm2, const uint8_t *mask2,
                      const StepBcast *bcast = nullptr, const double *zb = nullptr, const double *qb = nullptr);
-// pb_update.hip (15 states) / pb_update_rt21.hip: generic indexed (+ orientation, qm != NULL) update, m = 1..6
-int pbk_update15(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb,
-                 const double *qm, const uint8_t *mask);
-int pbk_update21(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb,
-                 const double *qm, const uint8_t *mask);
-// (pb_update_rt21.hip is built as three objects, by m)
-int pbk_update21_m123(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                      const uint8_t *mask);
-int pbk_update21_m45(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                     const uint8_t *mask);
-int pbk_update21_m6(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                    const uint8_t *mask);
-// pb_update_ct.hip: the same update on the cooperative mapping when idx is one of the handlers' lists and R is diagonal
-// (r2 = [m][B] device diagonal or NULL with rb2 = m broadcast values); -1 = no such kernel, use pbk_update15/21
-// zb / qb: HOST values of a measurement that is the same for every filter (kernel arguments instead of device blocks)
-int pbk_update_ct(pb_ctx *c, int m, const int *idx, const double *z, const double *r2, const double *rb2, const double *qm,
-                  const uint8_t *mask, const double *zb = nullptr, const double *qb = nullptr, const double *rfull = nullptr);
+// The inputs of a stand-alone indexed (+ orientation) update as the kernels take them: device blocks [rows][B], or host values that
+// travel as kernel arguments.  Exactly one of r_diag / r_bcast / r_full is set.
+struct UpdateIn {
+  const double *z = nullptr;        // [m][B]
+  const double *r_diag = nullptr;   // per-filter R diagonal [m][B]
+  const double *r_bcast = nullptr;  // one R diagonal for every filter: m HOST values
+  const double *r_full = nullptr;   // per-filter full R [m*m][B], column-major
+  const double *qm = nullptr;       // measured quaternion [4][B]
+  const uint8_t *mask = nullptr;    // [B] or NULL
+  const double *z_host = nullptr;   // UpdateChoice::host_args: z (m HOST values) ...
+  const double *q_host = nullptr;   // ... and the measured quaternion (4) of ONE measurement for every filter
+  int rkind() const { return r_full ? PB_R_FULL : r_bcast ? PB_R_DIAG_BROADCAST : PB_R_DIAG; }
+  const double *R() const { return r_full ? r_full : r_diag; }
+};
+// pb_update_ct.hip: THE entry to the update kernels -- launches what update_choice (pb_policy.hpp) answered; honours pb_set_output_slot
+int pbk_update(pb_ctx *c, const UpdateChoice &u, int m, const int *idx, const UpdateIn &in);
+// the run-time-index families and the 21-state list kernel, in the objects that hold them: pb_update.hip (15 states) and
+// pb_update_rt21.hip (built as three objects, by m)
+int pbk_update15(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
+int pbk_update21_m123(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
+int pbk_update21_m45(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
+int pbk_update21_m6(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
 // pb_smooth.hip
 int pbk_smooth_step(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);
 int pbk_smooth_wide(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);   // 15 states (pb_smooth_wide.hip)

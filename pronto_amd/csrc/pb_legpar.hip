@@ -14,7 +14,7 @@ static void launch_legpar(pb_ctx *c, double *out, const double *imu, const doubl
                           const LegStepArgs &la)
 {
   const LegParRows rows{ c->leg_blk, c->stride };
-  with_mem_hint(c->mem_hint, [&](auto mh) {
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) {
     constexpr int MH = decltype(mh)::value;
 #define LEG_ARGS c->st, out, c->B, imu, q[0], q[1], q[2], q[3], c->k, bc, c->leg_par, lin, c->leg_chain, la, rows
 #if PB_LEG_NS == 15

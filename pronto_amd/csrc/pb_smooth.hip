@@ -1,20 +1,11 @@
-// pb_smooth.hip -- launcher of the RTS smoother kernel (rbis_smooth.hpp); see pb_ctx.hpp.
+// pb_smooth.hip -- launcher of the RTS smoother kernel smooth_kernel (pb_policy.hpp) names (rbis_smooth.hpp, rbis_smooth_lane.hpp); see pb_ctx.hpp.
 #include "pb_ctx.hpp"
 #include "rbis_smooth.hpp"
 #include "rbis_smooth_lane.hpp"
 
 int pbk_smooth_step(pb_ctx *c, const double *np_, const double *ns_, const double *cu, double *out, double dt)
 {
-  // PRONTO_SMOOTH_PIVOT=1: Eigen's diagonal pivoting in the factorisation of P^- (the reference's .ldlt(); parity with the oracle at
-  // 1e-15); default: no pivot search (P^- is SPD; rbis_smooth.hpp)
-  static const bool pivot = getenv("PRONTO_SMOOTH_PIVOT") && getenv("PRONTO_SMOOTH_PIVOT")[0] == '1';
-  // PRONTO_SMOOTH_KERNEL=reg: the 16 / 32-lanes-per-filter kernel of rounds 2-4 (rbis_smooth.hpp); default: one lane per filter,
-  // the dense work split over role waves (rbis_smooth_lane.hpp)
-  static const bool reg_kernel = pivot || (getenv("PRONTO_SMOOTH_KERNEL") && !strcmp(getenv("PRONTO_SMOOTH_KERNEL"), "reg"));
-  // 15 states: k_smooth_wide (rbis_smooth_wide.hpp, pb_smooth_wide.hip: persistent workgroups, one wave per SIMD with 512 registers, data
-  // movement by whole rows) unless PRONTO_SMOOTH_KERNEL=lane asks for k_smooth_lane (two tiles per CU, 256 registers: the default until
-  // the second half of round 5, and still the kernel for 21 states)
-  static const bool lane15 = getenv("PRONTO_SMOOTH_KERNEL") && !strcmp(getenv("PRONTO_SMOOTH_KERNEL"), "lane");
+  const SmoothKernel kernel = smooth_kernel(c->policy);
   if (!c->smooth_attr) {  // more than the default 64 KB of dynamic LDS per workgroup
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_lane<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) SmoothLaneCfg<15>::LDS_BYTES));
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_lane<21>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) SmoothLaneCfg<21>::LDS_BYTES));
@@ -25,9 +16,10 @@ int pbk_smooth_step(pb_ctx *c, const double *np_, const double *ns_, const doubl
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_reg<21, false>), hipFuncAttributeMaxDynamicSharedMemorySize, l21));
     c->smooth_attr = true;
   }
-  if (!reg_kernel) {
+  if (kernel == SMOOTH_WIDE15) return pbk_smooth_wide(c, np_, ns_, cu, out, dt);
+  const bool pivot = kernel == SMOOTH_REG_PIVOT;   // (below: SMOOTH_LANE, or k_smooth_reg with / without the pivot search)
+  if (kernel == SMOOTH_LANE) {
     const dim3 grid((unsigned) ((c->B + 63) / 64));
-    if (c->ns == 15 && !lane15) return pbk_smooth_wide(c, np_, ns_, cu, out, dt);
     if (c->ns == 15) k_smooth_lane<15><<<grid, SmoothLaneCfg<15>::THREADS, SmoothLaneCfg<15>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
     else k_smooth_lane<21><<<grid, SmoothLaneCfg<21>::THREADS, SmoothLaneCfg<21>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, dt, c->k);
   } else if (c->ns == 15) {

@@ -12,10 +12,9 @@ int pbk_smooth_wide(pb_ctx *c, const double *np_, const double *ns_, const doubl
     HIPCHK(c, hipFuncSetAttribute(reinterpret_cast<const void *>(&k_smooth_wide<15>), hipFuncAttributeMaxDynamicSharedMemorySize, (int) SmoothWideCfg<15>::LDS_BYTES));
     c->smooth_wide_attr = true;
   }
-  // persistent: one workgroup per CU walks the tiles (PRONTO_SMOOTH_GRID: workgroups, for experiments)
-  static const int grid_env = getenv("PRONTO_SMOOTH_GRID") ? atoi(getenv("PRONTO_SMOOTH_GRID")) : 0;
-  const int ntiles = (c->B + 63) / 64, nwg = grid_env > 0 ? grid_env : c->n_cu;
-  k_smooth_wide<15><<<dim3((unsigned) (ntiles < nwg ? ntiles : nwg)), SmoothWideCfg<15>::THREADS, SmoothWideCfg<15>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, ntiles, dt,
+  // persistent: one workgroup per CU walks the tiles (smooth_wide_grid, pb_policy.hpp)
+  const int ntiles = (c->B + 63) / 64;
+  k_smooth_wide<15><<<dim3((unsigned) smooth_wide_grid(c->policy, ntiles, c->n_cu)), SmoothWideCfg<15>::THREADS, SmoothWideCfg<15>::LDS_BYTES, c->stream>>>(np_, ns_, cu, out, c->B, ntiles, dt,
                                                                                                                                        c->k);
   LAUNCHCHK(c);
 #ifdef SML_TIMELINE  // attribution build: print the stamps of launch 60 of scripts/smooth_rate.py

@@ -3,27 +3,30 @@
 #include "rbis_step_kernels.hpp"
 #include "rbis_replay_kernels.hpp"
 
-// The ONE launch of the step kernel this context runs: from `st` into `out`, a grid that covers nb filters (the inputs stay blocks
-// [rows][B] of the whole batch: the kernels take B as the row stride).  half: two workgroups per tile -- the whole-batch 15-state
-// cooperative launch only.
+// The ONE launch of the step kernel of a mapping (pb_policy.hpp): from `st` into `out`, a grid that covers nb filters (the inputs stay
+// blocks [rows][B] of the whole batch: the kernels take B as the row stride).  step.half: two workgroups per tile -- the whole-batch
+// 15-state cooperative launch only.
 template <bool UPDATE, int MH>
-static void launch_step_kernel(pb_ctx *c, const double *st, double *out, int nb, bool coop15, bool half, const double *imu, const double *lo,
+static void launch_step_kernel(pb_ctx *c, const double *st, double *out, int nb, StepChoice step, const double *imu, const double *lo,
                                const uint8_t *mask, const double q[4], const StepBcast &bc, const Consts &k)
 {
   const int B = c->B;
-  if (c->ns == 15 && coop15) {
+  switch (step.map) {
+  case MAP_COOP15: {
     Consts kk = k;
-    kk.half_tiles = half ? 1 : 0;   // (this launch only: every other kernel that takes c->k keeps whole tiles)
-    k_step_coop<15, UPDATE, MH><<<nblk(nb) * (half ? 2 : 1), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, CorrArgs(), bc);
-  } else if (c->ns == 15) {
+    kk.half_tiles = step.half ? 1 : 0;   // (this launch only: every other kernel that takes c->k keeps whole tiles)
+    k_step_coop<15, UPDATE, MH><<<nblk(nb) * (step.half ? 2 : 1), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], kk, CorrArgs(), bc);
+    break;
+  }
+  case MAP_LANE15:
     k_step<15, UPDATE, MH><<<(nb + PB_STEP_BLOCK - 1) / PB_STEP_BLOCK, PB_STEP_BLOCK, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, bc);
-  } else if (c->quad21) {
-    // n = 21: 231 packed covariance entries do not fit one lane's registers; four cooperating waves per tile at two waves
-    // per SIMD (rbis_quad.hpp): one launch, one state round trip.
+    break;
+  case MAP_QUAD21:
     k_step_quad<UPDATE, MH><<<nblk(nb), 256, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, bc);
-  } else {
-    // the two-wave cooperative kernel at one wave per SIMD (rbis_coop.hpp); PRONTO_BATCH_QUAD21=0
+    break;
+  case MAP_COOP21:
     k_step_coop<21, UPDATE, MH><<<nblk(nb), 128, 0, c->stream>>>(st, out, B, imu, lo, mask, q[0], q[1], q[2], q[3], k, CorrArgs(), bc);
+    break;
   }
 }
 
@@ -35,8 +38,8 @@ static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uin
   StepBcast bc = bcast;
   imu = pbk_idle_prepare(c, imu, bc, &rc);
   if (rc) return rc;
-  with_mem_hint(c->mem_hint, [&](auto mh) {
-    launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->coop15, c->half15, imu, lo, mask, q, bc, c->k);
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) {
+    launch_step_kernel<UPDATE, decltype(mh)::value>(c, c->st, out, c->B, c->policy.step, imu, lo, mask, q, bc, c->k);
   });
   LAUNCHCHK(c);
   if ((rc = pbk_idle_restore(c, out, nullptr, q))) return rc;
@@ -47,8 +50,8 @@ static int launch_step(pb_ctx *c, const double *imu, const double *lo, const uin
 // The fused step on the filters [b0, b0 + nb) only -- b0 and the batch multiples of 64 (whole tiles), the posterior in place, the inputs
 // still blocks [rows][B] of the WHOLE batch (the block is addressed by shifting every pointer, the per-filter process noise included:
 // the kernels count filters from 0, so an unshifted block would give every range the noise of filters 0..nb-1).
-// coop15 / mem_hint are the caller's: a block that fits the memory-side cache wants the kernel and the cache policy of ITS size.
-int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, bool coop15, int mem_hint)
+// map / mem_hint are the caller's: a block that fits the memory-side cache wants the kernel and the cache policy of ITS size.
+int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t *mask, const double q[4], long b0, int nb, Mapping map, int mem_hint)
 {
   if (c->st != c->st_base || c->out_slot >= 0 || (c->B & 63) || (b0 & 63) || (nb & 63) || b0 + nb > c->B)
     return fail(c, PB_ERR_STATE, "pbk_step_range: whole tiles of a head that lives in the context's own array");
@@ -58,7 +61,7 @@ int pbk_step_range(pb_ctx *c, const double *imu, const double *lo, const uint8_t
   Consts kk = c->k;   // (this launch only)
   if (kk.qblk) kk.qblk += b0;
   with_mem_hint(mem_hint, [&](auto mh) {
-    launch_step_kernel<true, decltype(mh)::value>(c, st, st, nb, coop15, false, imu + b0, lo + b0, mask_b, q, StepBcast(), kk);
+    launch_step_kernel<true, decltype(mh)::value>(c, st, st, nb, StepChoice{ map, false }, imu + b0, lo + b0, mask_b, q, StepBcast(), kk);
   });
   LAUNCHCHK(c);
   return PB_OK;
@@ -104,9 +107,7 @@ int pbk_step(pb_ctx *c, bool update, const double *imu, const double *lo, const 
 int pbk_step_leg(pb_ctx *c, const double *imu, const StepBcast *bcast, const double q[4], const LegIn &lin, int64_t utime, const LegMeasPar &mp,
                  double *lo_out, uint8_t *mask_out)
 {
-  // the two-wave 15-state mapping (the default up to 393 216 filters) and the four-wave 21-state mapping.  Mode lin_rate with
-  // leg_estimate's world constraint switched on needs the stand-alone kernel (mode pos_and_lin_rate tracks it inside the pair kernel).
-  if ((c->ns == 15 && !c->coop15) || (c->ns == 21 && !c->quad21) || (c->leg_par.world_constraint && mp.mode != 2)) return -1;
+  if (!pair_kernel_exists(c->policy.step.map, c->leg_par.world_constraint != 0, mp.mode)) return -1;
   StepBcast bc = bcast ? *bcast : StepBcast();
   LegStepArgs la{ c->legd, c->legi, c->stride, utime, mp.r_v2, mp.r_v2_uncertain, lo_out, mask_out, mp };
   double *out = update_target(c);
@@ -131,17 +132,13 @@ int pbk_replay_fused(pb_ctx *c, int T, const double *imu, const double *lo, cons
     so.base = slot_ptr(c, slot0);
     so.stride = c->state_doubles;
   }
-  // PRONTO_BATCH_REPLAY_ONELANE=1 (pb_create): the first, one-lane-per-filter version (15 states only; A/B runs)
-  if (c->ns == 15 && c->replay_onelane && slot0 < 0)
-    k_replay_fused<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k);
-  else if (c->ns == 15)
-    k_replay_coop<15><<<nblk(c->B), 128, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so);
-  else if (c->quad21)
-    // four waves per tile, register budget of ONE wave per SIMD: 3.3e9 steps/s at 64k filters, T = 32; cut for two waves
-    // per SIMD it carries 452 B of scratch and measured 2.4e9; the two-wave kernel below 1.7e9
-    k_replay_quad<1><<<nblk(c->B), 256, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so);
-  else
-    k_replay_coop<21><<<nblk(c->B), 128, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so);
+  switch (replay_kernel(c->policy, slot0 >= 0)) {
+  case REPLAY_LANE15: k_replay_fused<15><<<nblk(c->B), 64, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k); break;
+  case REPLAY_COOP15: k_replay_coop<15><<<nblk(c->B), 128, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so); break;
+  case REPLAY_QUAD21: k_replay_quad<1><<<nblk(c->B), 256, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so); break;
+  case REPLAY_COOP21: k_replay_coop<21><<<nblk(c->B), 128, 0, c->stream>>>(c->st, c->B, T, imu, lo, mask, q[0], q[1], q[2], q[3], c->k, so); break;
+  default: return fail(c, PB_ERR_STATE, "pbk_replay_fused: no kernel");
+  }
   LAUNCHCHK(c);
   return PB_OK;
 }
@@ -164,15 +161,14 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
     // slot is the first launch's (k_step_quad_pred / k_step_coop_pred<21>); the correction lands in the output slot.
     int rc = pbk_step(c, true, imu, lo, mask, q, bcast);
     if (rc) return rc;
-    static const int idx_po[6] = { 9, 10, 11, 6, 7, 8 }, idx_py[4] = { 9, 10, 11, 8 };
-    const int m2 = (corr_kind == PB_CORR_POS_ORIENT) ? 6 : 4;
-    const int *idx2 = (corr_kind == PB_CORR_POS_ORIENT) ? idx_po : idx_py;
+    const UpdateListRow &l = kUpdateLists[correction_list(corr_kind)];
     const int slot = pb_head_slot(c);  // a checkpointed step: the correction lands in the same slot
     if (slot >= 0) c->out_slot = slot;
-    rc = pbk_update_ct(c, m2, idx2, z2, r2, rb2, qm2, mask2, zb, qb);
-    if (rc >= 0) return rc;
-    if (!z2 || !qm2) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: no kernel takes this correction as arguments; stage the blocks");
-    return pbk_update21(c, m2, idx2, z2, r2 ? r2 : rb2, r2 ? PB_R_DIAG : PB_R_DIAG_BROADCAST, r2 ? nullptr : rb2, qm2, mask2);
+    const UpdateChoice u = correction_choice(c->policy.step.map, corr_kind, zb != nullptr, mask2 != nullptr);
+    if (zb && !u.host_args) return fail(c, PB_ERR_ARG, "pb_step_legodo_correct: no kernel takes this correction as arguments; stage the blocks");
+    UpdateIn in;
+    in.z = z2; in.r_diag = r2; in.r_bcast = rb2; in.qm = qm2; in.mask = mask2; in.z_host = zb; in.q_host = qb;
+    return pbk_update(c, u, l.m, l.idx, in);
   }
   CorrArgs ca;
   ca.z2 = z2; ca.r2 = r2; ca.qm2 = qm2; ca.mask2 = mask2;
@@ -195,7 +191,7 @@ int pbk_step_correct(pb_ctx *c, int corr_kind, const double *imu, const double *
   if (pred) {
     if (pbk_step_corr_pred_kernel(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc)) return fail(c, PB_ERR_STATE, "pb_step_legodo_correct: no kernel keeps the prediction here");
   } else {
-    with_mem_hint(c->mem_hint, [&](auto mh) {
+    with_mem_hint(c->policy.mem_hint, [&](auto mh) {
       if (corr_kind == PB_CORR_POS_ORIENT) launch_corr<15, decltype(mh)::value, CorrPosOrient>(c, out, imu, lo, mask, q, ca, bc);
       else launch_corr<15, decltype(mh)::value, CorrPosYaw>(c, out, imu, lo, mask, q, ca, bc);
     });

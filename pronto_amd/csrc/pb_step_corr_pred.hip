@@ -25,6 +25,6 @@ int pbk_step_corr_pred_kernel(pb_ctx *c, int corr_kind, double *out, double *pre
                               const double q[4], const CorrArgs &ca, const StepBcast &bc)
 {
   int rc = -1;
-  with_mem_hint(c->mem_hint, [&](auto mh) { rc = launch_corr_pred_mh<decltype(mh)::value>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc); });
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) { rc = launch_corr_pred_mh<decltype(mh)::value>(c, corr_kind, out, pred, imu, lo, mask, q, ca, bc); });
   return rc;
 }

@@ -28,7 +28,7 @@ template <int SIX>
 static void launch_step_leg_mh(pb_ctx *c, double *out, const double *imu, const double q[4], const StepBcast &bc, const LegIn &lin,
                                const LegStepArgs &la)
 {
-  with_mem_hint(c->mem_hint, [&](auto mh) { launch_step_leg<decltype(mh)::value, SIX>(c, out, imu, q, bc, lin, la); });
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) { launch_step_leg<decltype(mh)::value, SIX>(c, out, imu, q, bc, lin, la); });
 }
 
 #if PB_LEG_NS == 15

@@ -6,13 +6,14 @@
 #include "rbis_quad_rt.hpp"
 
 template <int NS, int M, int MH>
-static void launch_update_mh(pb_ctx *c, const IdxArg<M> &ia, const DiagArg<M> &da, const double *z, const double *R,
-                             int rkind, const double *qm, const uint8_t *mask)
+static void launch_update_mh(pb_ctx *c, const IdxArg<M> &ia, const DiagArg<M> &da, const UpdateIn &in)
 {
   double *out = update_target(c);
+  const double *z = in.z, *R = in.R(), *qm = in.qm;
+  const uint8_t *mask = in.mask;
+  const int rkind = in.rkind();
   if constexpr (M >= 5) {  // five / six gathered columns beside the covariance do not fit one lane: two waves per tile
-    // (two cache policies are built: non-temporal streaming falls back to the default one)
-    if (MH == MH_STORE_SC1)
+    if (two_policy_hint(MH) == MH_STORE_SC1)
       k_update_coop_rt<M, MH_STORE_SC1><<<nblk(c->B), 128, 0, c->stream>>>(c->st, out, c->B, ia, z, R, rkind, da, qm, mask, c->k);
     else
       k_update_coop_rt<M, MH_DEFAULT><<<nblk(c->B), 128, 0, c->stream>>>(c->st, out, c->B, ia, z, R, rkind, da, qm, mask, c->k);
@@ -26,38 +27,30 @@ static void launch_update_mh(pb_ctx *c, const IdxArg<M> &ia, const DiagArg<M> &d
 }
 
 template <int NS, int M>
-static void launch_update_m(pb_ctx *c, const int *idx, const double *z, const double *R, int rkind, const double *rb,
-                            const double *qm, const uint8_t *mask)
+static void launch_update_m(pb_ctx *c, const int *idx, const UpdateIn &in)
 {
   IdxArg<M> ia;
   DiagArg<M> da;
   for (int i = 0; i < M; i++) {
     ia.v[i] = idx[i];
-    da.v[i] = rb ? rb[i] : 0.0;
+    da.v[i] = in.r_bcast ? in.r_bcast[i] : 0.0;
   }
-  with_mem_hint(c->mem_hint, [&](auto mh) { launch_update_mh<NS, M, decltype(mh)::value>(c, ia, da, z, R, rkind, qm, mask); });
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) { launch_update_mh<NS, M, decltype(mh)::value>(c, ia, da, in); });
 }
 
-template <int NS>
-static int launch_update(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind,
-                         const double *rb, const double *qm, const uint8_t *mask)
+// family: UPD_LANE_RT (m <= 4) or UPD_COOP_RT (m = 5, 6), as update_choice answers them
+int pbk_update15(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in)
 {
+  if (family != (m <= 4 ? UPD_LANE_RT : UPD_COOP_RT)) return fail(c, PB_ERR_STATE, "update: no kernel of family %d for m = %d", (int) family, m);
   switch (m) {
-    case 1: launch_update_m<NS, 1>(c, idx, z, R, rkind, rb, qm, mask); break;
-    case 2: launch_update_m<NS, 2>(c, idx, z, R, rkind, rb, qm, mask); break;
-    case 3: launch_update_m<NS, 3>(c, idx, z, R, rkind, rb, qm, mask); break;
-    case 4: launch_update_m<NS, 4>(c, idx, z, R, rkind, rb, qm, mask); break;
-    case 5: launch_update_m<NS, 5>(c, idx, z, R, rkind, rb, qm, mask); break;
-    case 6: launch_update_m<NS, 6>(c, idx, z, R, rkind, rb, qm, mask); break;
-    default: return fail(c, PB_ERR_ARG, "update: m must be 1..6");
+    case 1: launch_update_m<15, 1>(c, idx, in); break;
+    case 2: launch_update_m<15, 2>(c, idx, in); break;
+    case 3: launch_update_m<15, 3>(c, idx, in); break;
+    case 4: launch_update_m<15, 4>(c, idx, in); break;
+    case 5: launch_update_m<15, 5>(c, idx, in); break;
+    case 6: launch_update_m<15, 6>(c, idx, in); break;
+    default: return fail(c, PB_ERR_STATE, "update: m must be 1..6");
   }
   LAUNCHCHK(c);
   return PB_OK;
-}
-
-
-int pbk_update15(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb,
-                 const double *qm, const uint8_t *mask)
-{
-  return launch_update<15>(c, m, idx, z, R, rkind, rb, qm, mask);
 }

@@ -5,67 +5,54 @@
 #include "rbis_quad_rt.hpp"
 
 template <int M>
-static int launch_rt21(pb_ctx *c, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                       const uint8_t *mask)
+static int launch_rt21(pb_ctx *c, UpdateFamily family, const int *idx, const UpdateIn &in)
 {
+  if (family != UPD_QUAD_RT) return fail(c, PB_ERR_STATE, "update: no 21-state kernel of family %d for m = %d", (int) family, M);
   IdxArg<M> ia;
   DiagArg<M> da;
   for (int i = 0; i < M; i++) {
     if (idx[i] < 0 || idx[i] > 20) return fail(c, PB_ERR_ARG, "update: index %d out of range", idx[i]);
     ia.v[i] = idx[i];
-    da.v[i] = rb ? rb[i] : 0.0;
+    da.v[i] = in.r_bcast ? in.r_bcast[i] : 0.0;
   }
   double *out = update_target(c);
-  // (two cache policies are built: non-temporal streaming falls back to the default one)
-  if (c->mem_hint == MH_STORE_SC1)
-    k_update_quad_rt<M, MH_STORE_SC1><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, ia, z, R, rkind, da, qm, mask, c->k);
+  if (two_policy_hint(c->policy.mem_hint) == MH_STORE_SC1)
+    k_update_quad_rt<M, MH_STORE_SC1><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, ia, in.z, in.R(), in.rkind(), da, in.qm, in.mask, c->k);
   else
-    k_update_quad_rt<M, MH_DEFAULT><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, ia, z, R, rkind, da, qm, mask, c->k);
+    k_update_quad_rt<M, MH_DEFAULT><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, ia, in.z, in.R(), in.rkind(), da, in.qm, in.mask, c->k);
   LAUNCHCHK(c);
   update_done(c, out);
   return PB_OK;
 }
 
 #if PB_UPD_MSET == 0
-int pbk_update21_m123(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                      const uint8_t *mask)
+int pbk_update21_m123(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in)
 {
-  if (m == 1) return launch_rt21<1>(c, idx, z, R, rkind, rb, qm, mask);
-  if (m == 2) return launch_rt21<2>(c, idx, z, R, rkind, rb, qm, mask);
-  return launch_rt21<3>(c, idx, z, R, rkind, rb, qm, mask);
+  if (m == 1) return launch_rt21<1>(c, family, idx, in);
+  if (m == 2) return launch_rt21<2>(c, family, idx, in);
+  return launch_rt21<3>(c, family, idx, in);
 }
 #elif PB_UPD_MSET == 1
-int pbk_update21_m45(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                     const uint8_t *mask)
+int pbk_update21_m45(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in)
 {
-  if (m == 4) return launch_rt21<4>(c, idx, z, R, rkind, rb, qm, mask);
-  return launch_rt21<5>(c, idx, z, R, rkind, rb, qm, mask);
+  if (m == 4) return launch_rt21<4>(c, family, idx, in);
+  return launch_rt21<5>(c, family, idx, in);
 }
 #else
-int pbk_update21_m6(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                    const uint8_t *mask)
+int pbk_update21_m6(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in)
 {
-  static const int lin_rot_rate[6] = { 3, 4, 5, 0, 1, 2 };  // rbis_legodo_common.cpp:66-67
-  if (!c->generic_update && memcmp(idx, lin_rot_rate, sizeof lin_rot_rate) == 0) {
+  if (family == UPD_QUAD_LIST) {  // LegOdoCommon's lin_rot_rate list [3,4,5,0,1,2] (update_choice)
     DiagArg<6> da;
-    for (int i = 0; i < 6; i++) da.v[i] = rb ? rb[i] : 0.0;
+    for (int i = 0; i < 6; i++) da.v[i] = in.r_bcast ? in.r_bcast[i] : 0.0;
     double *out = update_target(c);
-    if (c->mem_hint == MH_STORE_SC1)
-      k_update_quad_list<MH_STORE_SC1, 3, 4, 5, 0, 1, 2><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, z, R, rkind, da, qm, mask, c->k);
+    if (two_policy_hint(c->policy.mem_hint) == MH_STORE_SC1)
+      k_update_quad_list<MH_STORE_SC1, 3, 4, 5, 0, 1, 2><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, in.z, in.R(), in.rkind(), da, in.qm, in.mask, c->k);
     else
-      k_update_quad_list<MH_DEFAULT, 3, 4, 5, 0, 1, 2><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, z, R, rkind, da, qm, mask, c->k);
+      k_update_quad_list<MH_DEFAULT, 3, 4, 5, 0, 1, 2><<<nblk(c->B), 256, 0, c->stream>>>(c->st, out, c->B, in.z, in.R(), in.rkind(), da, in.qm, in.mask, c->k);
     LAUNCHCHK(c);
     update_done(c, out);
     return PB_OK;
   }
-  return launch_rt21<6>(c, idx, z, R, rkind, rb, qm, mask);
-}
-int pbk_update21(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *rb, const double *qm,
-                 const uint8_t *mask)
-{
-  if (m >= 1 && m <= 3) return pbk_update21_m123(c, m, idx, z, R, rkind, rb, qm, mask);
-  if (m == 4 || m == 5) return pbk_update21_m45(c, m, idx, z, R, rkind, rb, qm, mask);
-  if (m == 6) return pbk_update21_m6(c, m, idx, z, R, rkind, rb, qm, mask);
-  return fail(c, PB_ERR_ARG, "update: m must be 1..6");
+  return launch_rt21<6>(c, family, idx, in);
 }
 #endif

@@ -235,7 +235,7 @@ __global__ __launch_bounds__(64) void k_step_yawlock(const double *st, double *s
 template <int NS, int MODE>
 void launch_step(pb_ctx *c, double *out, const YawIn &yin, const LegIn &lin, int64_t utime, double *z_out, double *quat_out, uint8_t *mask_out)
 {
-  with_mem_hint(c->mem_hint, [&](auto mh) {
+  with_mem_hint(c->policy.mem_hint, [&](auto mh) {
     k_step_yawlock<NS, MODE, decltype(mh)::value><<<nblk(c->B), 64, 0, c->stream>>>(c->st, out, c->B, c->stride, c->yaw_par, yin, lin, c->leg_chain,
                                                                                   utime, c->yawd, c->yawi, z_out, quat_out, mask_out, c->k);
   });

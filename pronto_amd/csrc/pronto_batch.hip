@@ -39,73 +39,13 @@ extern "C" int pb_create(pb_ctx **out, int n_states, int batch, int device, int 
   c->dev = device;
   c->nsnap = n_snapshots;
   c->n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  {
-    // 15-state hot kernel: the two-wave cooperative mapping (2 waves/SIMD, reads and writes interleave) measured
-    // 3-20 % faster up to 256k filters, the one-lane-per-filter k_step 3-5 % faster beyond (profiles/).
-    // PRONTO_BATCH_COOP15=0/1 forces one of them (A/B runs and tests).
-    const char *e = getenv("PRONTO_BATCH_COOP15");
-    c->coop15 = e ? (e[0] == '1') : (batch <= 393216);
-    // Below ~48k filters the two-wave kernel's 64-filter tiles leave workgroup slots empty (1 024 slots: 256 CUs x 4 workgroups of two
-    // waves at two waves per SIMD; 32 768 filters = 512 tiles).  Two workgroups per tile, 32 filters each, fill them -- and change
-    // nothing: 13.12 against 13.14 us at 32 768 filters, slower everywhere else (profiles/r05_half_tile.txt).  The step time is
-    // ~5 us of one tile's dependent chain + bytes / 9.4 TB/s at every size; more workgroups do not shorten the chain.  Kept as an A/B
-    // switch (PRONTO_BATCH_HALF=1), off by default.
-    const char *eh = getenv("PRONTO_BATCH_HALF");
-    c->half15 = c->coop15 && n_states == 15 && eh && eh[0] == '1';
-    // (read here, per context, as the other switches: a function-local static kept the FIRST call's value for the whole process)
-    const char *er = getenv("PRONTO_BATCH_REPLAY_ONELANE");
-    c->replay_onelane = er && er[0] == '1';
-  }
   c->stride = ((long) batch + 63) / 64 * 64;
   c->nc = (n_states == 15) ? Lay<15>::NC : Lay<21>::NC;
   c->state_doubles = (size_t) c->stride * (size_t) ((n_states == 15) ? Slots<15>::NSLOT : Slots<21>::NSLOT);
-  {
-    // XCD-contiguous tile order: each of the 8 XCDs walks one contiguous range of tiles instead of every 8th tile.  With
-    // the tiled layout it measured equal or faster for both state sizes at every batch size (n = 21 at 192k filters:
-    // 162 -> 146 us).  PRONTO_BATCH_XCD=0/1 forces it either way for A/B runs.
-    const char *e = getenv("PRONTO_BATCH_XCD");
-    c->k.xcd_remap = e ? (e[0] == '1') : 1;
-    // Cache policy of the state round trip (rbis_tile_io.hpp MemHint), measured on both step kernels: a state that
-    // fits the XCDs' L2s (< ~48 MB) wants the default policy (sc1 stores 7 % slower at 32k x 15 states); up to ~1.3x
-    // the 256 MB memory-side cache sc1 stores are 1-4 % faster; beyond, non-temporal loads+stores are 7-15 % faster
-    // (1M filters: 469 -> 417 us) and 10-40 % SLOWER if used on a cache-sized state.  PRONTO_BATCH_MEMHINT=0/1/2 forces.
-    const long state_bytes = (long) c->state_doubles * 8;
-    const char *gu = getenv("PRONTO_BATCH_GENERIC_UPDATE");
-    c->generic_update = gu && gu[0] == '1';
-    const char *q21 = getenv("PRONTO_BATCH_QUAD21");
-    c->quad21 = !(q21 && q21[0] == '0');
-    const char *h = getenv("PRONTO_BATCH_MEMHINT");
-    c->mem_hint = h ? (h[0] - '0')
-                    : (state_bytes < (48L << 20)    ? MH_DEFAULT
-                       : state_bytes < (310L << 20) ? MH_STORE_SC1
-                       : state_bytes < (350L << 20) ? MH_DEFAULT   // (160k 21-state filters, 336 MB: 112.6 us against 124.8 with sc1 stores, 118.7 non-temporal)
-                                                    : MH_STREAM_NT);
-    if (c->mem_hint < 0 || c->mem_hint > 2) c->mem_hint = MH_DEFAULT;
-    // Bulk replays of a state that does not fit the memory-side cache (pb_run_legodo): filter range outer, time inner, over blocks
-    // of whole tiles whose state stays cache-resident from step to step -- the filters are independent and the streams are known
-    // up front (the reference's own many-runs workload replays one log 8 000 times, state-estimator/python/param_sweep.py:39-52).
-    // Same T = 1 accounting: every step still loads and stores every posterior once, the round trip just ends in the cache.
-    // Block size: the largest that measured at the cache-resident rate (profiles/r05_batch_sweep.txt), the blocks made equal;
-    // each block runs the kernel and the cache policy of ITS size.  PRONTO_BATCH_BLOCKED=0 / 1 switches it off / on for any
-    // size, PRONTO_BATCH_BLOCK_FILTERS=<n> names the block size.
-    {
-      const char *eb = getenv("PRONTO_BATCH_BLOCKED"), *ef = getenv("PRONTO_BATCH_BLOCK_FILTERS");
-      const long per_filter = state_bytes / c->stride;
-      // (15 states: 224k filters = 257 MB of state per block measured best, 0.87 of the roofline at 512k / 1 M filters with 64-step
-      // streams against 0.74 step by step; 21 states: 112k = 237 MB, 0.84 against 0.67 -- profiles/r05_batch_sweep.txt)
-      long want = ef ? atol(ef) : (n_states == 15 ? 229376 : 114688);
-      want = (want + 63) / 64 * 64;
-      const bool on = eb ? (eb[0] == '1') : (state_bytes > (256L << 20));
-      if (on && want >= 64 && want < batch && (batch & 63) == 0) {
-        const long nblocks = (batch + want - 1) / want;
-        c->run_block = (int) (((batch + nblocks - 1) / nblocks + 63) / 64 * 64);
-        const long blk_bytes = (long) c->run_block * per_filter;
-        c->run_block_hint = h ? c->mem_hint : (blk_bytes < (48L << 20) ? MH_DEFAULT : MH_STORE_SC1);
-        const char *e15 = getenv("PRONTO_BATCH_COOP15");
-        c->run_block_coop15 = e15 ? (e15[0] == '1') : true;
-      }
-    }
-  }
+  static_assert(Slots<15>::NSLOT == state_slots(15) && Slots<21>::NSLOT == state_slots(21), "pb_policy.hpp: state_slots");
+  // which kernels, grids and cache policies this context runs: decided once, here, from the switches as they are NOW (pb_policy.hpp)
+  c->policy = make_policy(n_states, batch, (long) c->state_doubles * 8, read_switches());
+  c->k.xcd_remap = c->policy.xcd_remap ? 1 : 0;
   // The kernels address the STATE through one buffer descriptor per 64-filter tile (64-bit tile base), so its size is
   // bounded by HBM only; the per-message INPUT blocks ([rows][B], at most 36 rows) go through one 32-bit-ranged
   // descriptor each, which bounds the batch of one context at 2^32 / (36 * 8) filters.
@@ -202,16 +142,12 @@ extern "C" int pb_sync(pb_ctx *c)
   return PB_OK;
 }
 
-extern "C" int pb_run_block(const pb_ctx *c) { return c ? c->run_block : 0; }
+extern "C" int pb_run_block(const pb_ctx *c) { return c ? c->policy.run_block : 0; }
 
 extern "C" const char *pb_hot_kernel(const pb_ctx *c)
 {
   if (!c) return "";
-  static const char *const names[4][3] = { { "k_step_quad<true,0>", "k_step_quad<true,1>", "k_step_quad<true,2>" },
-                                           { "k_step_coop<21,true,0>", "k_step_coop<21,true,1>", "k_step_coop<21,true,2>" },
-                                           { "k_step_coop<15,true,0>", "k_step_coop<15,true,1>", "k_step_coop<15,true,2>" },
-                                           { "k_step<15,true,0>", "k_step<15,true,1>", "k_step<15,true,2>" } };
-  return names[c->ns == 21 ? (c->quad21 ? 0 : 1) : (c->coop15 ? 2 : 3)][c->mem_hint];
+  return step_kernel_name(c->policy.step.map, c->policy.mem_hint);
 }
 extern "C" int pb_batch(const pb_ctx *c) { return c ? c->B : -1; }
 extern "C" int pb_n_states(const pb_ctx *c) { return c ? c->ns : -1; }
@@ -533,9 +469,7 @@ extern "C" int pb_step_legodo_correct(pb_ctx *c, const double *imu_block, const 
   const int m2 = (corr_kind == PB_CORR_POS_ORIENT) ? 6 : 4;
   const size_t B = (size_t) c->B;
   const bool rbc = r_kind2 == PB_R_DIAG_BROADCAST;
-  // (the two-wave 21-state mapping, PRONTO_BATCH_QUAD21=0, has no m = 6 kernel that takes z / quat_meas as arguments:
-  // its correction falls back to the generic update, which needs the replicated blocks staged below)
-  const bool arg_kernel = c->ns == 15 || c->quad21 || m2 <= 4;
+  const bool arg_kernel = correction_as_args(c->policy.step.map, corr_kind);
   Part p[7] = { { imu_block, sizeof(double) * 7 * B, 0 }, { lo_block, sizeof(double) * 6 * B, 0 }, { mask, B, 0 },
                 { z2, sizeof(double) * m2 * B, 0 }, { rbc ? nullptr : R2, rbc ? 0 : sizeof(double) * m2 * B, 0 },
                 { quat_meas2, sizeof(double) * 4 * B, 0 }, { mask2, B, 0 } };
@@ -568,13 +502,14 @@ extern "C" int pb_run_legodo(pb_ctx *c, int n_steps, const double *imu_stream, c
   if (n_steps < 0 || !imu_stream || !lo_stream || !q) return fail(c, PB_ERR_ARG, "pb_run_legodo: bad argument");
   const size_t B = (size_t) c->B;
   if (int rc = timed_begin(c, elapsed_ms)) return rc;
-  if (c->run_block > 0 && n_steps > 1 && c->st == c->st_base && c->out_slot < 0) {
+  const Policy &pol = c->policy;
+  if (pol.run_block > 0 && n_steps > 1 && c->st == c->st_base && c->out_slot < 0) {
     // cache-blocked order (pb_create): every block of filters runs the whole stream before the next block starts
-    for (long b0 = 0; b0 < (long) B; b0 += c->run_block) {
-      const int nb = (int) std::min<long>(c->run_block, (long) B - b0);
+    for (long b0 = 0; b0 < (long) B; b0 += pol.run_block) {
+      const int nb = (int) std::min<long>(pol.run_block, (long) B - b0);
       for (int s = 0; s < n_steps; s++) {
         int rc = pbk_step_range(c, imu_stream + (size_t) s * 7 * B, lo_stream + (size_t) s * 6 * B,
-                                mask_stream ? mask_stream + (size_t) s * B : nullptr, q, b0, nb, c->run_block_coop15, c->run_block_hint);
+                                mask_stream ? mask_stream + (size_t) s * B : nullptr, q, b0, nb, pol.run_block_map, pol.run_block_hint);
         if (rc) return rc;
       }
     }
@@ -638,39 +573,27 @@ int pbk_update_common(pb_ctx *c, int m, const int *idx, const double *z, const d
   }
   const size_t B = (size_t) c->B;
   size_t rbytes;
-  const double *rb = nullptr;
   if (mem == PB_HOST_BROADCAST && rkind == PB_R_DIAG) rkind = PB_R_DIAG_BROADCAST;  // the same thing, without a fill
-  if (rkind == PB_R_DIAG_BROADCAST) { rb = R; rbytes = 0; }
+  if (rkind == PB_R_DIAG_BROADCAST) rbytes = 0;
   else if (rkind == PB_R_DIAG) rbytes = sizeof(double) * m * B;
   else if (rkind == PB_R_FULL) rbytes = sizeof(double) * m * m * B;
   else return fail(c, PB_ERR_ARG, "update: bad r_kind %d", rkind);
-  int rc;
-  if (mem == PB_HOST_BROADCAST && rb && !mask && !c->generic_update) {
-    // one measurement for every filter on a compile-time-index kernel: z, R and the quaternion are kernel arguments
-    rc = pbk_update_ct(c, m, idx, nullptr, nullptr, rb, nullptr, nullptr, z, orient ? qm : nullptr);
-    if (rc >= 0) return rc;
+  const UpdateChoice u = update_choice(c->policy.step.map, c->policy.generic_update, m, idx, orient, rkind, mem == PB_HOST_BROADCAST, mask != nullptr);
+  UpdateIn in;
+  if (rkind == PB_R_DIAG_BROADCAST) in.r_bcast = R;
+  if (u.host_args) {  // one measurement for every filter on a compile-time-index kernel: z, R and the quaternion are kernel arguments
+    in.z_host = z;
+    in.q_host = orient ? qm : nullptr;
+    return pbk_update(c, u, m, idx, in);
   }
-  Part p[4] = { { z, sizeof(double) * m * B, 0 }, { rb ? nullptr : R, rbytes, 0 },
+  Part p[4] = { { z, sizeof(double) * m * B, 0 }, { in.r_bcast ? nullptr : R, rbytes, 0 },
                 { orient ? qm : nullptr, sizeof(double) * 4 * B, 0 }, { mask, B, 0 } };
-  rc = stage_in(c, mem, p, 4);
-  if (rc) return rc;
-  // the handlers' own index lists run on the compile-time-index kernels (two-role for 15 states, four-wave for 21; no column gather);
-  // PRONTO_BATCH_GENERIC_UPDATE=1 forces the run-time-index kernel for A/B runs and tests
-  if (!c->generic_update && (rkind == PB_R_DIAG || rkind == PB_R_DIAG_BROADCAST)) {
-    rc = pbk_update_ct(c, m, idx, (const double *) p[0].dev, rb ? nullptr : (const double *) p[1].dev, rb,
-                       (const double *) p[2].dev, (const uint8_t *) p[3].dev);
-    if (rc >= 0) return rc;
-  }
-  if (!c->generic_update && rkind == PB_R_FULL) {  // a full per-filter R on the handlers' index lists: same kernels
-    rc = pbk_update_ct(c, m, idx, (const double *) p[0].dev, nullptr, nullptr, (const double *) p[2].dev, (const uint8_t *) p[3].dev,
-                       nullptr, nullptr, (const double *) p[1].dev);
-    if (rc >= 0) return rc;
-  }
-  if (c->ns == 15)
-    return pbk_update15(c, m, idx, (const double *) p[0].dev, (const double *) p[1].dev, rkind, rb,
-                        (const double *) p[2].dev, (const uint8_t *) p[3].dev);
-  return pbk_update21(c, m, idx, (const double *) p[0].dev, (const double *) p[1].dev, rkind, rb,
-                      (const double *) p[2].dev, (const uint8_t *) p[3].dev);
+  if (int rc = stage_in(c, mem, p, 4)) return rc;
+  in.z = (const double *) p[0].dev;
+  (rkind == PB_R_FULL ? in.r_full : in.r_diag) = (const double *) p[1].dev;
+  in.qm = (const double *) p[2].dev;
+  in.mask = (const uint8_t *) p[3].dev;
+  return pbk_update(c, u, m, idx, in);
 }
 
 extern "C" int pb_update_indexed(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int r_kind,

@@ -33,8 +33,7 @@ __device__ __forceinline__ void group_sync()
 
 // =================================================================================================================
 // k_smooth_reg<NS>: the same step with the factorisation in REGISTERS and every run-time index turned into an LDS
-// ADDRESS.  This is the kernel pb_smooth_step launches; k_smooth_step above is kept as the A/B reference
-// (PRONTO_BATCH_SMOOTH_LDS=1).
+// ADDRESS.  (Round 1's k_smooth_step, everything resident in LDS, and its switch were removed in round 2.)
 //
 // The LDS kernel is a chain of dependent LDS read-modify-write round trips (PMC: 65 % of wave time waiting, ~180 k
 // cycles per wave) at 1.75 waves per SIMD, and its row-per-lane global loads touch 16 component rows x 4 filters per

@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "pb_policy.hpp"
 #include "rbis_device.hpp"
 
 // workgroup size of the one-lane hot kernel = one tile
@@ -65,10 +66,8 @@ __device__ __forceinline__ void stg2(rsrc_t r, unsigned soff, unsigned voff, d2_
   asm volatile("s_nop 1" ::"v"(d));
 }
 
-// Memory hint of the state round trip in the step kernels (template parameter MH), picked by the host from the state
-// size: while the state fits the 256 MB memory-side cache, stores with sc1 (write through the XCD's L2) are
-// a few % faster; far beyond it, non-temporal loads AND stores are; in between neither helps.
-enum { MH_DEFAULT = 0, MH_STORE_SC1 = 1, MH_STREAM_NT = 2 };
+// Memory hint of the state round trip in the step kernels (template parameter MH): the MH_* constants and the host's pick from the
+// state size are pb_policy.hpp's; here, the cache-policy bits of the loads (LA) and stores (SA) each stands for.
 template <int MH> struct MemHint {
   static constexpr int LA = (MH == MH_STREAM_NT) ? 2 : 0;
   static constexpr int SA = (MH == MH_STORE_SC1) ? 16 : (MH == MH_STREAM_NT) ? 2 : 0;
