@@ -157,7 +157,20 @@ int pb_update_indexed(pb_ctx *ctx, int m, const int *idx, const double *z, const
 int pb_update_indexed_orient(pb_ctx *ctx, int m, const int *idx, const double *z, const double *R, int r_kind,
                              const double *quat_meas, const uint8_t *mask, int mem);
 
-/* Fused hot step = RBISIMUProcessStep then RBISIndexedMeasurement(idx = velocityInds = {3,4,5}) as produced
+#define PB_UPDATE_WIDE_MAX_ROWS 9
+/* RBISIndexedMeasurement / RBISIndexedPlusOrientationMeasurement::updateFilter for index lists of up to nine rows
+ * (rbis.cpp:160-217; the GPF's all_states list {3..11}, rgbd_gpf_lib.cpp:86-91).  quat_meas == NULL: no orientation.
+ * m in 1..9: up to six rows take exactly the path of pb_update_indexed / pb_update_indexed_orient (same kernel, same bits);
+ * seven to nine run k_update_wide (one lane per filter, the measured columns in LDS); more is PB_ERR_ARG.  The two calls
+ * above keep refusing m > 6.  Honoured as there: idx in range and distinct; all three pb_rkind encodings; mask [B];
+ * PB_HOST, PB_DEVICE and PB_HOST_BROADCAST inputs (broadcast: mask must be NULL; a broadcast full R is expanded on the
+ * device); pb_set_output_slot; a pending pb_set_pred_slot is refused; z entries at chi indices are ignored under an
+ * orientation measurement; ONE log of the product of the pivots (rbis.cpp:142: NaN for a negative determinant).  A masked-off
+ * filter keeps its state bit for bit. */
+int pb_update_indexed_wide(pb_ctx *ctx, int m, const int *idx, const double *z, const double *R, int r_kind,
+                           const double *quat_meas, const uint8_t *mask, int mem);
+
+/* Fused hot step =RBISIMUProcessStep then RBISIndexedMeasurement(idx = velocityInds = {3,4,5}) as produced
  * by LegOdoCommon::createMeasurement in mode lin_rate (rbis_legodo_common.cpp:153-156): ONE launch and ONE
  * round trip of the state through HBM (BASELINE.json's "predict+update step").
  * lo_block [6][B] = z xyz, Rdiag xyz; mask as above. */

@@ -653,6 +653,17 @@ class BatchEstimator:
             pq, mq = _ptr_block(quat_meas, 4, self.B)
             self._chk(self._L.pb_update_indexed_orient(self._h, m, ia, pz, pr, kind, pq, pm, _same_mem(mz, mr, mm, mq)))
 
+    def update_indexed_wide(self, idx, z, R, mask=None, quat_meas=None):
+        """update_indexed for index lists of up to nine rows (pb_update_indexed_wide: the GPF's all_states list, velocity + chi +
+        position).  Up to six rows run exactly what update_indexed runs; z and R as there."""
+        m = len(idx)
+        ia = (C.c_int * m)(*[int(i) for i in idx])
+        pz, mz = _ptr_block(z, m, self.B)
+        _keep, pr, kind, mr = self._r(R, m)
+        pm, mm = _ptr(mask, np.uint8, shape=(self.B,))
+        pq, mq = (None, None) if quat_meas is None else _ptr_block(quat_meas, 4, self.B)
+        self._chk(self._L.pb_update_indexed_wide(self._h, m, ia, pz, pr, kind, pq, pm, _same_mem(mz, mr, mm, mq)))
+
     def step_legodo(self, imu_block, lo_block, mask, q4):
         """IMU block and leg-odometry block (+ mask) may live in different spaces (e.g. a broadcast [7] IMU message and a
         per-filter device measurement from legodo_update(..., after_predict=imu)): pb_step_legodo_split."""

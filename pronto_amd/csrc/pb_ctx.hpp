@@ -3,9 +3,9 @@
 // argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp), never a kernel: each .hip
 // includes the kernel headers it launches from, so every kernel is compiled in one object.  WHICH kernel a launcher runs is decided in
 // pb_policy.hpp (host-only, tested on the CPU): the context keeps one Policy, made in pb_create.
-// (the kernels are instantiated in twenty-one objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
-// pb_step_corr_pred.hip, pb_step_leg.hip and pb_legpar.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m -- and
-// pb_update_ct.hip the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
+// (the kernels are instantiated in twenty-two objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// pb_step_corr_pred.hip, pb_step_leg.hip and pb_legpar.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m --,
+// pb_update_ct.hip and pb_update_wide.hip (seven to nine rows, with its entry point pb_update_indexed_wide) the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
 // and entry points of the C ABI share one unit: pb_legodo.hip leg odometry and joint filters, pb_yawlock.hip, pb_frontend.hip the IMU
 // front end, pb_score.hip the ground-truth scorer; pb_history.hip the checkpoint slots and whole-log smoothing, which launches through
 // pbk_* only; pronto_batch.hip the context, staging, steps, updates and read-back).
@@ -383,6 +383,8 @@ int pbk_update15(pb_ctx *c, UpdateFamily family, int m, const int *idx, const Up
 int pbk_update21_m123(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
 int pbk_update21_m45(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
 int pbk_update21_m6(pb_ctx *c, UpdateFamily family, int m, const int *idx, const UpdateIn &in);
+// pb_update_wide.hip: family UPD_WIDE, m = 7 ... 9 (k_update_wide, rbis_update_wide.hpp)
+int pbk_update_wide(pb_ctx *c, int m, const int *idx, const UpdateIn &in);
 // pb_smooth.hip
 int pbk_smooth_step(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);
 int pbk_smooth_wide(pb_ctx *c, const double *next_pred, const double *next_sm, const double *cur, double *out, double dt);   // 15 states (pb_smooth_wide.hip)
@@ -392,3 +394,5 @@ int pbk_slot_select(pb_ctx *c, double *dst, const double *src, const uint8_t *ma
 // honours pb_set_output_slot
 int pbk_update_common(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *qm, bool orient,
                       const uint8_t *mask, int mem);
+// its check of an index list: every index inside the state, no index twice
+int pbk_check_indices(pb_ctx *c, int m, const int *idx);

@@ -222,6 +222,7 @@ enum UpdateFamily {
   UPD_LANE_RT,      // k_update_lane_rt<15,M,ORIENT>: run-time index list, the whole 15-state filter in one lane's registers (m <= 4)
   UPD_COOP_RT,      // k_update_coop_rt<M>: m = 5, 6, where the one-lane kernel spills: two waves per tile
   UPD_QUAD_RT,      // k_update_quad_rt<M>: run-time index list, 21 states
+  UPD_WIDE,         // k_update_wide<NS,M,ORIENT>: 7 ... 9 rows (pb_update_indexed_wide), one lane per filter, the measured columns in LDS
 };
 // the index lists the handlers produce; the rows up to CorrGpfZ in the order of the CORR types of rbis_coop.hpp
 enum UpdateList { LIST_VEL, LIST_POS, LIST_POS_VEL, LIST_POS_ORIENT, LIST_POS_YAW, LIST_VEL_YAW, LIST_YAW, LIST_GPF_YAW_POS, LIST_GPF_CHI_POS,
@@ -279,6 +280,14 @@ inline UpdateChoice update_choice(Mapping map, bool generic_update, int m, const
   // (kept as it was: the argument form is not offered under a mask, although the kernels that take it honour one)
   u.host_args = all_broadcast && rkind == PB_R_DIAG_BROADCAST && !masked && u.family <= UPD_LANE_LIST;
   return u;
+}
+
+// pb_update_indexed_wide (up to PB_UPDATE_WIDE_MAX_ROWS rows): up to six rows go wherever update_choice sends them; seven to nine run
+// k_update_wide (rbis_update_wide.hpp), whose inputs are always device blocks -- it has no argument form.
+inline UpdateChoice wide_update_choice(Mapping map, bool generic_update, int m, const int *idx, bool orient, int rkind, bool all_broadcast, bool masked)
+{
+  if (m <= 6) return update_choice(map, generic_update, m, idx, orient, rkind, all_broadcast, masked);
+  return { UPD_WIDE, LIST_NONE, false };
 }
 
 // pb_step_legodo_correct's correction (enum pb_corr) on the handlers' lists

@@ -37,6 +37,7 @@ static int launch_list(pb_ctx *c, UpdateFamily family, double *out, const CorrAr
 // THE entry to the update kernels: launches the (family, list) update_choice answered (pb_policy.hpp)
 int pbk_update(pb_ctx *c, const UpdateChoice &u, int m, const int *idx, const UpdateIn &in)
 {
+  if (u.family == UPD_WIDE) return pbk_update_wide(c, m, idx, in);
   if (u.family == UPD_LANE_RT || u.family == UPD_COOP_RT) return pbk_update15(c, u.family, m, idx, in);
   if (u.family == UPD_QUAD_RT || u.family == UPD_QUAD_LIST)
     return m <= 3 ? pbk_update21_m123(c, u.family, m, idx, in) : m <= 5 ? pbk_update21_m45(c, u.family, m, idx, in) : pbk_update21_m6(c, u.family, m, idx, in);

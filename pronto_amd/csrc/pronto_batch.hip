@@ -47,8 +47,8 @@ extern "C" int pb_create(pb_ctx **out, int n_states, int batch, int device, int 
   c->policy = make_policy(n_states, batch, (long) c->state_doubles * 8, read_switches());
   c->k.xcd_remap = c->policy.xcd_remap ? 1 : 0;
   // The kernels address the STATE through one buffer descriptor per 64-filter tile (64-bit tile base), so its size is
-  // bounded by HBM only; the per-message INPUT blocks ([rows][B], at most 36 rows) go through one 32-bit-ranged
-  // descriptor each, which bounds the batch of one context at 2^32 / (36 * 8) filters.
+  // bounded by HBM only; the per-message INPUT blocks ([rows][B], at most 36 rows; pb_update_indexed_wide checks its up to 81 itself)
+  // go through one 32-bit-ranged descriptor each, which bounds the batch of one context at 2^32 / (36 * 8) filters.
   if ((unsigned long long) batch * 36ull * 8ull >= (1ull << 32)) {
     delete c;
     return fail(nullptr, PB_ERR_ARG, "pb_create: batch %d too large for one context (input blocks must stay below 4 GiB; "
@@ -560,17 +560,23 @@ extern "C" int pb_replay_legodo_checkpointed(pb_ctx *c, int n_steps, int steps_p
   return replay_impl(c, "pb_replay_legodo_checkpointed", n_steps, steps_per_launch, imu_stream, lo_stream, mask_stream, q, true, first_slot, elapsed_ms);
 }
 
+int pbk_check_indices(pb_ctx *c, int m, const int *idx)
+{
+  for (int i = 0; i < m; i++) {
+    if (idx[i] < 0 || idx[i] >= c->ns) return fail(c, PB_ERR_ARG, "update: index %d out of range for n_states=%d", idx[i], c->ns);
+    for (int j = 0; j < i; j++)
+      if (idx[i] == idx[j]) return fail(c, PB_ERR_ARG, "update: duplicate index %d", idx[i]);
+  }
+  return PB_OK;
+}
+
 int pbk_update_common(pb_ctx *c, int m, const int *idx, const double *z, const double *R, int rkind, const double *qm, bool orient,
                       const uint8_t *mask, int mem)
 {
   if (m < 1 || m > 6) return fail(c, PB_ERR_ARG, "update: m must be 1..6 (got %d)", m);
   if (!idx || !z || !R) return fail(c, PB_ERR_ARG, "update: NULL input");
   if (orient && !qm) return fail(c, PB_ERR_ARG, "update: quat_meas is NULL");
-  for (int i = 0; i < m; i++) {
-    if (idx[i] < 0 || idx[i] >= c->ns) return fail(c, PB_ERR_ARG, "update: index %d out of range for n_states=%d", idx[i], c->ns);
-    for (int j = 0; j < i; j++)
-      if (idx[i] == idx[j]) return fail(c, PB_ERR_ARG, "update: duplicate index %d", idx[i]);
-  }
+  if (int rc = pbk_check_indices(c, m, idx)) return rc;
   const size_t B = (size_t) c->B;
   size_t rbytes;
   if (mem == PB_HOST_BROADCAST && rkind == PB_R_DIAG) rkind = PB_R_DIAG_BROADCAST;  // the same thing, without a fill

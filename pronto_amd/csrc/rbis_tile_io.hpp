@@ -204,7 +204,7 @@ struct SlotOut {
 
 // PB_HOST_BROADCAST inputs: dst [rows][B] <- one value per row (k_fill_rows, rbis_util_kernels.hpp; pronto_batch.hip stage_in)
 struct RowVals {
-  static constexpr int MAX = 36;  // the largest block of one call: a full 6 x 6 measurement covariance
+  static constexpr int MAX = 81;  // the largest block of one call: a full 9 x 9 measurement covariance (pb_update_indexed_wide)
   double v[MAX];
 };
 
