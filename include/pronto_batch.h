@@ -764,6 +764,46 @@ int pb_calib_copy_checksum(pb_ctx *ctx, int reps, uint64_t out[2]);
 int pb_set_utime(pb_ctx *ctx, int64_t utime);
 int64_t pb_get_utime(const pb_ctx *ctx);
 
+/* ---- Gaussian particle filter measurement (state-estimator/src/gpf/gpf.hpp:53-192, rbis_gpf_update.cpp:28-76) -------
+ * The front half of a GPF update for every filter of the batch: draw K states from the marginal of the rows idx (m = 1..9,
+ * distinct, inside the state), score them, fit the weighted and the unweighted cloud, solve for the effective measurement.
+ * The outputs z_eff [m][B] / R_eff [m*m][B] are exactly the blocks pb_update_indexed_wide(..., PB_R_FULL, ..., PB_DEVICE)
+ * takes: applying them is that call's.  All blocks are device memory, [rows][B] doubles; sample-indexed blocks are
+ * [K][rows][B].  None of these calls writes the filter or takes a pending pb_set_pred_slot / pb_set_output_slot.
+ * PB_ERR_ARG: m outside 1..9, repeated or out-of-range indices, K < 1, a NULL block, a grid call before pb_gpf_grid_set. */
+
+/* [rows][B] standard normals, counter-based (no state in the context: any (filter, row) can be reproduced).
+ * Philox4x32-10 with key (seed low, seed high) and counter (filter b, row pair j = row / 2, stream_id, 0); from its words
+ * w0..w3: u1 = (((w0 2^32 + w1) >> 11) + 0.5) 2^-53, u2 likewise from w2, w3; row 2j = sqrt(-2 ln u1) cos(2 pi u2),
+ * row 2j + 1 = sqrt(-2 ln u1) sin(2 pi u2). */
+int pb_gpf_normals(pb_ctx *ctx, uint64_t seed, uint32_t stream_id, int rows, double *out_dev);
+/* xi [K][m][B] (standard normals) -> delta [K][m][B], s_k = L xi_k with L the lower Cholesky factor of P[idx, idx]
+ * (gpf.hpp:68-94), and pose [K][7][B]: position xyz then quaternion wxyz of the head with vec[idx_i] += s_k[i] and chi
+ * folded into the quaternion under the context's tolerance (gpf.hpp:97-103; what RBIS::getBotTrans hands a likelihood).
+ * A filter whose P[idx, idx] is not positive definite: delta = 0, every sample is the head, the fit reports status 2. */
+int pb_gpf_sample(pb_ctx *ctx, int m, const int *idx, int K, const double *xi_dev, double *delta_out_dev, double *pose_out_dev);
+/* delta [K][m][B], loglik [K][B] -> z_eff [m][B], R_eff [m*m][B] column-major, status int32 [B] (gpf.hpp:106-200):
+ * w_k = exp(l_k - max l), W = sum w_k.  Unless 5 m < W < max_weight_proportion K (both strict): R_eff = 1e4 I,
+ * z_eff = x[idx], status 2.  Otherwise (mean, cov) of the samples with unit weights (u) and with w (cov = sum w (x - mean)
+ * (x - mean)^T / sum w, no K - 1 correction); R_eff = (C_w^-1 - C_u^-1)^-1; z_eff = x[idx] + K_eff^-1 (mean_w - mean_u) with
+ * K_eff^T = (P[idx, idx] + R_eff)^-1 C_u; then the eigenvalues of R_eff below zero are set to 1e4 (status 1, else 0).
+ * Status 2 also for a filter with a non-finite loglik or a cloud whose covariance is not positive definite.  Bit-identical
+ * from run to run. */
+int pb_gpf_measurement(pb_ctx *ctx, int m, const int *idx, int K, const double *delta_dev, const double *loglik_dev,
+                       double max_weight_proportion, double *z_eff_out_dev, double *R_eff_out_dev, int32_t *status_out_dev);
+/* The built-in likelihood: evaluateScanLogLikelihood + evaluatePointLogLikelihood (LaserLikelihoodInterface.cpp:5-77) over a
+ * dense voxel grid in place of the octomap.  values_host double [nz][ny][nx] (dims = nx, ny, nz): what
+ * -node->getLogOdds() would return; copied, the array is free on return.  resolution, cov_scaling > 0. */
+int pb_gpf_grid_set(pb_ctx *ctx, const double origin[3], double resolution, const int dims[3], const double *values_host,
+                    double unknown_loglike, double cov_scaling);
+/* pose [K][7][B] (pb_gpf_sample) -> loglik [K][B].  points: n_points body-frame points, rows x0, y0, z0, x1, ...:
+ * [3 n_points][B] (PB_DEVICE, PB_HOST) or [3 n_points] host doubles (PB_HOST_BROADCAST: one robot's scan for every
+ * filter).  Per sample and point: p_map = R(q) p + t; a coordinate below origin or above origin + dims resolution scores
+ * unknown_loglike, else the voxel min((int) floor((c - origin_c) / resolution), dim_c - 1) per axis; loglik = sum /
+ * cov_scaling.  A point whose x is not finite is skipped (the reference's point_status filter). */
+int pb_gpf_grid_loglik(pb_ctx *ctx, int K, const double *pose_dev, int n_points, const double *points, int points_mem,
+                       double *loglik_out_dev);
+
 /* library identification: "pronto_batch <version> gfx950" */
 const char *pb_version(void);
 

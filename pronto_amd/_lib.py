@@ -99,6 +99,12 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_int]),
     "pb_update_indexed_wide": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_void_p, C.c_void_p, C.c_int,
                                          C.c_void_p, C.c_void_p, C.c_int]),
+    "pb_gpf_normals": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p]),
+    "pb_gpf_sample": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pb_gpf_measurement": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p,
+                                     C.c_void_p, C.c_void_p]),
+    "pb_gpf_grid_set": (C.c_int, [C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int), C.c_void_p, C.c_double, C.c_double]),
+    "pb_gpf_grid_loglik": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "pb_step_legodo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_int]),
     "pb_step_legodo_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp]),
     "pb_step_legodo_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_int, C.c_int, C.c_void_p,

@@ -664,6 +664,100 @@ class BatchEstimator:
         pq, mq = (None, None) if quat_meas is None else _ptr_block(quat_meas, 4, self.B)
         self._chk(self._L.pb_update_indexed_wide(self._h, m, ia, pz, pr, kind, pq, pm, _same_mem(mz, mr, mm, mq)))
 
+    # --- Gaussian particle filter measurement (pb_gpf_*) ---
+    def _gpf_dev(self, a, shape, dtype=np.float64):
+        """a device tensor of `shape` from a torch tensor or a numpy array (uploaded); the shape is checked before any ABI call"""
+        import torch
+        if tuple(a.shape) != tuple(shape):
+            raise ValueError("expected an array of shape %s, got %s" % (tuple(shape), tuple(a.shape)))
+        want = {np.float64: torch.float64, np.int32: torch.int32}[dtype]
+        t = torch.as_tensor(a) if not _is_torch(a) else a
+        if t.dtype != want:
+            raise TypeError("expected %s values" % want)
+        return t.to("cuda:%d" % self.device).contiguous()
+
+    def _gpf_empty(self, shape, dtype=None):
+        import torch
+        return torch.empty(shape, dtype=dtype or torch.float64, device="cuda:%d" % self.device)
+
+    @staticmethod
+    def _gpf_idx(idx, K):
+        m = len(idx)
+        if not 1 <= m <= 9:
+            raise ValueError("the GPF takes 1..9 rows (got %d)" % m)
+        if int(K) < 1:
+            raise ValueError("K must be at least 1")
+        return m, (C.c_int * m)(*[int(i) for i in idx])
+
+    def gpf_normals(self, seed, stream_id, rows):
+        """[rows, B] standard normals on the device, counter-based: Philox4x32-10 keyed by seed over (filter, row pair, stream_id),
+        Box-Muller (pb_gpf_normals).  The same arguments give the same bits."""
+        if int(rows) < 1:
+            raise ValueError("rows must be at least 1")
+        out = self._gpf_empty((int(rows), self.B))
+        self._chk(self._L.pb_gpf_normals(self._h, int(seed) & (2 ** 64 - 1), int(stream_id) & (2 ** 32 - 1), int(rows), C.c_void_p(out.data_ptr())))
+        return out
+
+    def gpf_sample(self, idx, xi):
+        """xi [K, m, B] standard normals -> (delta [K, m, B], pose [K, 7, B]) device tensors: K draws from the marginal of the rows idx
+        of every filter and the poses (position xyz, quaternion wxyz) of the sampled states (pb_gpf_sample)."""
+        K = xi.shape[0]
+        m, ia = self._gpf_idx(idx, K)
+        x = self._gpf_dev(xi, (K, m, self.B))
+        delta, pose = self._gpf_empty((K, m, self.B)), self._gpf_empty((K, 7, self.B))
+        self._chk(self._L.pb_gpf_sample(self._h, m, ia, K, C.c_void_p(x.data_ptr()), C.c_void_p(delta.data_ptr()), C.c_void_p(pose.data_ptr())))
+        return delta, pose
+
+    def gpf_measurement(self, idx, delta, loglik, max_weight_proportion=0.999):
+        """delta [K, m, B], loglik [K, B] -> (z_eff [m, B], R_eff [m*m, B], status int32 [B]) device tensors, the blocks
+        update_indexed_wide takes (pb_gpf_measurement).  status 0: as computed, 1: negative eigenvalues of R_eff replaced, 2: the weights
+        are ill-conditioned, R_eff = 1e4 I and z_eff = x[idx]."""
+        import torch
+        K = delta.shape[0]
+        m, ia = self._gpf_idx(idx, K)
+        d, l = self._gpf_dev(delta, (K, m, self.B)), self._gpf_dev(loglik, (K, self.B))
+        z, R, status = self._gpf_empty((m, self.B)), self._gpf_empty((m * m, self.B)), self._gpf_empty((self.B,), torch.int32)
+        self._chk(self._L.pb_gpf_measurement(self._h, m, ia, K, C.c_void_p(d.data_ptr()), C.c_void_p(l.data_ptr()), float(max_weight_proportion),
+                                             C.c_void_p(z.data_ptr()), C.c_void_p(R.data_ptr()), C.c_void_p(status.data_ptr())))
+        return z, R, status
+
+    def gpf_grid_set(self, origin, resolution, values, unknown_loglike, cov_scaling):
+        """The built-in likelihood's map: values [nz, ny, nx] (numpy; what -node->getLogOdds() would return), origin (3), resolution."""
+        v = np.ascontiguousarray(values, dtype=np.float64)
+        if v.ndim != 3 or len(origin) != 3:
+            raise ValueError("values must be [nz, ny, nx] and origin have three entries")
+        o = (C.c_double * 3)(*[float(a) for a in origin])
+        dims = (C.c_int * 3)(v.shape[2], v.shape[1], v.shape[0])
+        self._chk(self._L.pb_gpf_grid_set(self._h, o, float(resolution), dims, C.c_void_p(v.ctypes.data), float(unknown_loglike), float(cov_scaling)))
+
+    def gpf_grid_loglik(self, pose, points):
+        """pose [K, 7, B] -> loglik [K, B] (device tensor) of the scan `points`: [3 n, B] per filter (torch device tensor or numpy), or a
+        1-D numpy array of 3 n values, one robot's scan for every filter (pb_gpf_grid_loglik).  Points with a non-finite x are skipped."""
+        K = pose.shape[0]
+        if K < 1:
+            raise ValueError("K must be at least 1")
+        p = self._gpf_dev(pose, (K, 7, self.B))
+        if points.shape[0] % 3:
+            raise ValueError("points must have 3 n rows")
+        n = points.shape[0] // 3
+        pp, mem = _ptr_block(points, 3 * n, self.B)
+        out = self._gpf_empty((K, self.B))
+        self._chk(self._L.pb_gpf_grid_loglik(self._h, K, C.c_void_p(p.data_ptr()), n, pp, mem, C.c_void_p(out.data_ptr())))
+        return out
+
+    def gpf_update(self, idx, K, loglik_fn, seed, stream_id=0, max_weight_proportion=0.999, mask=None):
+        """One whole GPF update: normals -> samples -> loglik_fn(pose [K, 7, B]) -> [K, B] (any torch function of the poses, or
+        self.gpf_grid_loglik) -> the effective measurement -> update_indexed_wide.  Returns (z_eff, R_eff, status)."""
+        m = len(idx)
+        xi = self.gpf_normals(seed, stream_id, int(K) * m).view(int(K), m, self.B)
+        delta, pose = self.gpf_sample(idx, xi)
+        z, R, status = self.gpf_measurement(idx, delta, loglik_fn(pose), max_weight_proportion)
+        if mask is not None and not _is_torch(mask):      # (z and R are device blocks: the mask goes where they are)
+            import torch
+            mask = torch.as_tensor(np.ascontiguousarray(mask, dtype=np.uint8)).to(z.device)
+        self.update_indexed_wide(idx, z, R, mask=mask)
+        return z, R, status
+
     def step_legodo(self, imu_block, lo_block, mask, q4):
         """IMU block and leg-odometry block (+ mask) may live in different spaces (e.g. a broadcast [7] IMU message and a
         per-filter device measurement from legodo_update(..., after_predict=imu)): pb_step_legodo_split."""
