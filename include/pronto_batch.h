@@ -804,6 +804,39 @@ int pb_gpf_grid_set(pb_ctx *ctx, const double origin[3], double resolution, cons
 int pb_gpf_grid_loglik(pb_ctx *ctx, int K, const double *pose_dev, int n_points, const double *points, int points_mem,
                        double *loglik_out_dev);
 
+/* ---- Optical-flow sigma-point update (RBISOpticalFlowMeasurement, rbis_update_interface.cpp:109-260) -----------------
+ * The reference's one nonlinear measurement z = h(x): four rows (ux, uy, theta, scale) of a camera looking at the ground,
+ * taken by an unscented update with the reference's hard-coded weights (a2 = 1e-6, b = 2, k = 0, n = 21; :199-206).  One
+ * launch per message; h reads rows 0 ... 11 of the state only, so the update factors twelve columns of P and evaluates h 25
+ * times where the reference takes 43 sigma points off the full factor -- algebraically the same update. */
+
+/* The camera, once per context (OpticalFlowHandler's constructor, sensor_handlers.cpp:726-731): body_to_cam_trans is r, and
+ * zeta1, zeta2, eta are what RBISOpticalFlowMeasurement's constructor takes (rbis_update_interface.hpp:146-148): the COLUMNS
+ * of the Eigen matrix that bot_trans_get_rot_mat_3x3 filled row-major, i.e. the ROWS of libbot's body -> camera rotation. */
+int pb_flow_set_camera(pb_ctx *ctx, const double body_to_cam_trans[3], const double zeta1[3], const double zeta2[3],
+                       const double eta[3]);
+/* flags bit 0: the orientation h sees is quat_head * Exp(chi_sigma) (what addState would give).  Default 0 is the reference:
+ * RBIS(state_vec) of :113 starts from the identity, so the orientation is Exp(chi_sigma) where |chi_sigma| exceeds the fold
+ * tolerance of pb_set_constants and the identity otherwise; the head's quaternion does not enter. */
+#define PB_FLOW_HEAD_QUAT 1
+/* RBISOpticalFlowMeasurement::updateFilter (:160-260) with measure (:111-138) for every filter.
+ * flow_block [7][B] (or [7] host doubles under PB_HOST_BROADCAST): ux, uy, theta, scale -- z_meas, sensor_handlers.cpp:748-751
+ * -- then alpha1, alpha2, gamma (:753-755).  R is 4 x 4 in the three pb_rkind encodings, as for pb_update_indexed (the
+ * handler's is diag(r_ux, r_uy, r_r, r_s)^2, :735-742).  mask [B] uint8 or NULL; mem = PB_HOST, PB_DEVICE or
+ * PB_HOST_BROADCAST (broadcast: mask must be NULL), as for pb_update_indexed_wide.  pb_set_output_slot is honoured, a pending
+ * pb_set_pred_slot is refused; PB_ERR_STATE before pb_flow_set_camera.
+ * As in the reference the posterior is the prior with vec += K (z_meas - zhat), NOT folded (:257; the next predict's addState
+ * folds chi), P -= K Pzz K^T (:258); the quaternion and the log-likelihood keep the prior's bits (:163,190).  Pzz is factored
+ * by the unpivoted LDL^T of the other updates (:254).  There is no guard on the height term (:191-192 is commented out):
+ * non-finite results show up in pb_summary.
+ * zhat_out DEVICE [4][B] or NULL: the predicted measurement the reference publishes as OPTICAL_FLOW_PSEUDO (:140-158,236);
+ * written for the filters with status 0 only.
+ * status_out DEVICE int32 [B] or NULL: 0 applied; 1 masked off; 2 + k: pivot k (0 ... 11) of the Cholesky factor of P is not
+ * positive or not finite -- the filter keeps its state bit for bit.  (The reference returns only when the factor holds a
+ * NaN and otherwise goes on with what Eigen's failed LLT left behind, :211-217; that is not imitated.) */
+int pb_update_optical_flow(pb_ctx *ctx, const double *flow_block, const double *R, int r_kind, const uint8_t *mask, int mem,
+                           int flags, double *zhat_out, int32_t *status_out);
+
 /* library identification: "pronto_batch <version> gfx950" */
 const char *pb_version(void);
 

@@ -18,6 +18,7 @@ PB_HOST, PB_DEVICE, PB_HOST_BROADCAST = 0, 1, 2
 PB_R_DIAG_BROADCAST, PB_R_DIAG, PB_R_FULL = 0, 1, 2
 PB_CORR_POS_ORIENT, PB_CORR_POS_YAW = 0, 1
 PB_SLOT_HEAD = -1
+PB_FLOW_HEAD_QUAT = 1
 PB_SCORE_DRIFT, PB_SCORE_ABS = 1, 2
 PB_SCORE_ROWS, PB_SCORE_COUNTS = 35, 5
 PB_SCORE_MEAN_PDDT, PB_SCORE_RMS_DRIFT, PB_SCORE_ATE_RMSE = 0, 1, 2
@@ -105,6 +106,8 @@ _SIGS = {
                                      C.c_void_p, C.c_void_p]),
     "pb_gpf_grid_set": (C.c_int, [C.c_void_p, _dp, C.c_double, C.POINTER(C.c_int), C.c_void_p, C.c_double, C.c_double]),
     "pb_gpf_grid_loglik": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "pb_flow_set_camera": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
+    "pb_update_optical_flow": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "pb_step_legodo": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_int]),
     "pb_step_legodo_split": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, _dp]),
     "pb_step_legodo_correct": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_int, C.c_int, C.c_void_p,

@@ -664,6 +664,36 @@ class BatchEstimator:
         pq, mq = (None, None) if quat_meas is None else _ptr_block(quat_meas, 4, self.B)
         self._chk(self._L.pb_update_indexed_wide(self._h, m, ia, pz, pr, kind, pq, pm, _same_mem(mz, mr, mm, mq)))
 
+    # --- optical-flow sigma-point update (pb_flow_set_camera, pb_update_optical_flow) ---
+    def flow_set_camera(self, body_to_cam_trans, zeta1, zeta2, eta):
+        """The camera of update_optical_flow: its position in the body frame and zeta1, zeta2, eta as RBISOpticalFlowMeasurement's
+        constructor takes them, the rows of the body -> camera rotation (pb_flow_set_camera)."""
+        args = []
+        for v in (body_to_cam_trans, zeta1, zeta2, eta):
+            a = np.ascontiguousarray(v, dtype=np.float64)
+            if a.shape != (3,):
+                raise ValueError("expected 3 values, got shape %s" % (a.shape,))
+            args.append((C.c_double * 3)(*a))
+        self._chk(self._L.pb_flow_set_camera(self._h, *args))
+
+    def update_optical_flow(self, flow_block, R, mask=None, flags=0, want_zhat=False, want_status=False):
+        """RBISOpticalFlowMeasurement: the four-row unscented update of every filter (pb_update_optical_flow).  flow_block [7,B] (or a
+        1-D numpy array of 7 values: one message for every filter): ux, uy, theta, scale, alpha1, alpha2, gamma; R: length-4 list
+        (broadcast diagonal), [4,B] or [16,B] full column-major; flags: PB_FLOW_HEAD_QUAT.  Returns (zhat [4,B] or None, status [B]
+        int32 or None), device tensors: the predicted measurement (filters with status 0 only; NaN elsewhere) and 0 applied /
+        1 masked off / 2 + k pivot k of the factor of P not positive."""
+        import torch
+        pf, mf = _ptr_block(flow_block, 7, self.B)
+        _keep, pr, kind, mr = self._r(R, 4)
+        pm, mm = _ptr(mask, np.uint8, shape=(self.B,))
+        dev = "cuda:%d" % self.device
+        zhat = torch.full((4, self.B), float("nan"), dtype=torch.float64, device=dev) if want_zhat else None
+        status = torch.empty((self.B,), dtype=torch.int32, device=dev) if want_status else None
+        self._chk(self._L.pb_update_optical_flow(self._h, pf, pr, kind, pm, _same_mem(mf, mr, mm), int(flags),
+                                                 C.c_void_p(zhat.data_ptr()) if want_zhat else None,
+                                                 C.c_void_p(status.data_ptr()) if want_status else None))
+        return zhat, status
+
     # --- Gaussian particle filter measurement (pb_gpf_*) ---
     def _gpf_dev(self, a, shape, dtype=np.float64):
         """a device tensor of `shape` from a torch tensor or a numpy array (uploaded); the shape is checked before any ABI call"""

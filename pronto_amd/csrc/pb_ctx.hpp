@@ -1,13 +1,13 @@
 // pb_ctx.hpp -- the context behind the C ABI, the owner of its device memory (dev_alloc / dev_release) and what crosses the translation
 // units of libpronto_batch.so: the per-call guard, the input resolver and the launchers.  It includes the
-// argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp, rbis_gpf.hpp), never a kernel: each .hip
+// argument types of the kernels (rbis_tile_io.hpp, rbis_coop.hpp, rbis_legodo.hpp, rbis_jointfilt.hpp, rbis_yawlock.hpp, rbis_score.hpp, rbis_gpf.hpp, rbis_flow.hpp), never a kernel: each .hip
 // includes the kernel headers it launches from, so every kernel is compiled in one object.  WHICH kernel a launcher runs is decided in
 // pb_policy.hpp (host-only, tested on the CPU): the context keeps one Policy, made in pb_create.
-// (the kernels are instantiated in twenty-three objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
+// (the kernels are instantiated in twenty-four objects so that they compile in parallel, see the Makefile: pb_step.hip, pb_step_pred.hip,
 // pb_step_corr_pred.hip, pb_step_leg.hip and pb_legpar.hip -- one object per state size -- the step kernels; pb_update.hip, pb_update_rt21.hip -- three objects, by m --,
 // pb_update_ct.hip and pb_update_wide.hip (seven to nine rows, with its entry point pb_update_indexed_wide) the update kernels; pb_smooth.hip and pb_smooth_wide.hip the smoother; pb_select.hip.  A family's kernels, launchers
 // and entry points of the C ABI share one unit: pb_legodo.hip leg odometry and joint filters, pb_yawlock.hip, pb_frontend.hip the IMU
-// front end, pb_score.hip the ground-truth scorer, pb_gpf.hip the GPF measurement; pb_history.hip the checkpoint slots and whole-log smoothing, which launches through
+// front end, pb_score.hip the ground-truth scorer, pb_gpf.hip the GPF measurement, pb_flow.hip the optical-flow update; pb_history.hip the checkpoint slots and whole-log smoothing, which launches through
 // pbk_* only; pronto_batch.hip the context, staging, steps, updates and read-back).
 #pragma once
 
@@ -30,6 +30,7 @@
 #include "rbis_yawlock.hpp"
 #include "rbis_score.hpp"
 #include "rbis_gpf.hpp"
+#include "rbis_flow.hpp"
 
 using namespace pb;
 
@@ -94,6 +95,10 @@ struct pb_ctx {
   double *gpf_grid = nullptr, *gpf_pts = nullptr;
   size_t gpf_grid_n = 0, gpf_pts_n = 0;
   bool gpf_grid_on = false;
+  // the optical-flow update (pb_flow_set_camera, rbis_flow.hpp): the camera and the reference's five sigma-point weights
+  FlowCam flow_cam;
+  FlowWeights flow_wt;
+  bool flow_cam_on = false;
   double *notch = nullptr;  // IMU notch cascade state [36][stride] (pb_imu_notch_init)
   NotchCoef notch_coef;
   bool notch_ready = false;

@@ -277,6 +277,47 @@ struct update_t {
 };
 
 // ---------------------------------------------------------------------------------------------------------------
+// pronto::optical_flow_t  (pronto_optical_flow_t.lcm; consumed by OpticalFlowHandler::processMessage, sensor_handlers.cpp:745-763,
+// published as OPTICAL_FLOW_PSEUDO by RBISOpticalFlowMeasurement::publish, rbis_update_interface.cpp:140-158).  Fixed-size.  The
+// member order is the .lcm file's: scale BEFORE theta, where the measurement vector is ux, uy, theta, scale.
+// ---------------------------------------------------------------------------------------------------------------
+struct optical_flow_t {
+  int64_t utime = 0;
+  double dt = 0, ux = 0, uy = 0, scale = 0, theta = 0, alpha1 = 0, alpha2 = 0, gamma = 0, conf_rs = 0, conf_xy = 0;
+
+  static const std::vector<Member> &members()
+  {
+    static const std::vector<Member> m = { { "utime", "int64_t", {} }, { "dt", "double", {} },      { "ux", "double", {} },
+                                           { "uy", "double", {} },     { "scale", "double", {} },   { "theta", "double", {} },
+                                           { "alpha1", "double", {} }, { "alpha2", "double", {} },  { "gamma", "double", {} },
+                                           { "conf_rs", "double", {} }, { "conf_xy", "double", {} } };
+    return m;
+  }
+  static uint64_t fingerprint() { static const uint64_t f = lcm_fingerprint(members()); return f; }
+  void encode(std::vector<uint8_t> &out) const
+  {
+    Writer w;
+    w.u64(fingerprint());
+    w.i64(utime);
+    const double v[10] = { dt, ux, uy, scale, theta, alpha1, alpha2, gamma, conf_rs, conf_xy };
+    w.f64s(v, 10);
+    out.swap(w.buf);
+  }
+  int decode(const void *data, size_t len)
+  {
+    Reader r(data, len);
+    if (r.u64() != fingerprint()) return r.ok ? WIRE_ERR_FINGERPRINT : WIRE_ERR_SHORT;
+    utime = r.i64();
+    double v[10];
+    r.f64s(v, 10);
+    if (!r.ok) return WIRE_ERR_SHORT;
+    dt = v[0]; ux = v[1]; uy = v[2]; scale = v[3]; theta = v[4];
+    alpha1 = v[5]; alpha2 = v[6]; gamma = v[7]; conf_rs = v[8]; conf_xy = v[9];
+    return (int) r.pos;
+  }
+};
+
+// ---------------------------------------------------------------------------------------------------------------
 // pronto::controller_status_t / pronto::behavior_t (pronto_controller_status_t.lcm, pronto_behavior_t.lcm): the two status
 // channels YawLockHandler listens to (rbis_yawlock_update.cpp:30-41).  Both are fixed-size.
 // ---------------------------------------------------------------------------------------------------------------
